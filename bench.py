@@ -1,26 +1,30 @@
 #!/usr/bin/env python
 """Benchmark of the SVI hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one full SVI step of velocity inference on the BASELINE.json workload (synthetic
 50k cells x 2k genes): guide sampling -> ELBO + reparameterised gradient (HIP) -> [all-reduce over
 cell shards when N > 1] -> ClippedAdam update.  N > 1: launched by torch.distributed.run, one rank per
 GPU, cells sharded contiguously (strong scaling: the problem is fixed, value = steps/s of the job).
 
-The timed region of --steps K steps (after --warmup W untimed ones), bracketed by barrier + synchronize and
-maximised over ranks, is REPEATED (--repeats, default 9): `value` / `ms_per_step` are the MEDIAN repeat, `repeat_ms`
-lists every repeat (the first ones show a clock that has not ramped yet: K = 20 steps are 4 ms of GPU work),
-`device_clock_mhz` is the shader clock measured on the device right after the timed region.
+`value` / `ms_per_step` time ONE region of exactly --steps K steps, after --warmup W untimed ones, bracketed by
+barrier + synchronize and maximised over ranks.  --dump-outputs DIR then writes what that path hands its caller after
+its last step (the guide's parameters and the step's loss) as DIR/<name>.npy; data and Philox draws are seeded, so the
+same arguments give the same inputs on every run.
 
-Prints ONE JSON line (rank 0).  Besides the contract keys it carries
+A plain run does only that and prints ONE JSON line (rank 0).  --full adds everything else after the headline region:
+  repeats       --repeats further regions of K steps each (default max(9, ceil(1000 / K))), listed in
+                `repeat_ms_per_step` (the first ones show a clock that has not ramped yet: K = 20 steps are 4 ms of GPU
+                work), and `device_clock_mhz`, the shader clock measured on the device before and after the timed regions,
   roofline      HIP-event timing of the likelihood kernel (>= 100 launches) against the HBM roof (ALGORITHMIC
                 bytes: fp32 count matrices read once, 8*Ng*Nc for the joint workload) and, under `valu`, against the
                 kernel's own arithmetic bound (static VALU count of the cell loop x measured issue cost),
   cpu_baseline  the oracle restatement (op-by-op torch fp32 + autograd + ClippedAdam) timed on this
                 host's cores on a bounded sample of the same workload (rank 0, N=1 only),
   modes         steps/s of the tutorial flow (velocity conditioned on the phase fit, default LRMN guide) and of
-                phase_inference at the same size, next to the headline.
+                phase_inference at the same size, next to the headline,
+  and the loss read-back rates, the opt-in loss_every=10 step and, for N > 1, the weak-scaling block.
 """
 import argparse
 import json
@@ -68,6 +72,11 @@ def parse():
     ap.add_argument("--conditions", type=int, default=1,
                     help="velocity modes: samples / conditions (Nx = Nb = this; > 1 adds the per-batch offsets Δν); the cells "
                          "are split evenly over them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the parameters and the loss of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: repeated regions, clock, roofline, loss read-back, other modes, CPU baseline, "
+                         "weak scaling (the --no-* and the options below select among them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-modes", action="store_true")
     ap.add_argument("--no-loss-every-demo", action="store_true",
@@ -75,9 +84,9 @@ def parse():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cpu-sample-cells", type=int, default=10000)
     ap.add_argument("--repeats", type=int, default=0,
-                    help="timed regions of --steps steps each, the median is reported; 0 = max(9, ceil(1000 / steps)): "
-                         "short regions are repeated until ~1000 steps are timed (the sustained clock under this load takes ~30 ms "
-                         "of GPU work to ramp, a 20-step region is 3 ms)")
+                    help="--full: further timed regions of --steps steps each, listed with their median; 0 = max(9, ceil(1000 / "
+                         "steps)): short regions are repeated until ~1000 steps are timed (the sustained clock under this load "
+                         "takes ~30 ms of GPU work to ramp, a 20-step region is 3 ms)")
     ap.add_argument("--roofline-launches", type=int, default=100)
     ap.add_argument("--no-weak", action="store_true",
                     help="N > 1: skip the weak-scaling block (--cells cells PER RANK, same kernels) that follows the strong run")
@@ -113,6 +122,41 @@ def median(xs):
     ys = sorted(xs)
     n = len(ys)
     return ys[n // 2] if n % 2 else 0.5 * (ys[n // 2 - 1] + ys[n // 2])
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+_ASCII = str.maketrans({"ν": "nu", "Δ": "d", "ϕ": "phi", "γ": "gamma", "β": "beta", "ω": "omega"})
+
+
+def step_outputs(engine, run, dist_on):
+    """What the timed path hands its caller after its last step, as fit() returns it: every parameter block of the guide
+    (unconstrained, float32; the per-cell phase locations gathered over ranks) and that step's loss (float64)."""
+    import numpy as np
+    out = {"param_" + n.translate(_ASCII): v.detach().cpu().numpy() for n, v in engine.named().items()}
+    if dist_on:
+        import torch.distributed as dist
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, out["param_phixy_locs"])
+        out["param_phixy_locs"] = np.concatenate(parts)
+    out["loss"] = np.array([run.loss_hist[run.step_idx - 1].item()], dtype=np.float64)
+    return out
+
+
+def dump_outputs(arrays, path):
+    """DIR/<name>.npy for every array.  Past DUMP_BUDGET_BYTES in all (only the per-cell blocks grow with --cells), an array
+    larger than its share keeps a fixed seeded sample of its rows, whose indices go to <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        share = DUMP_BUDGET_BYTES // (2 * len(arrays))
+        for name in list(arrays):
+            a = arrays[name]
+            if a.nbytes > share:
+                keep = max(1, share // max(1, a.nbytes // a.shape[0]))
+                rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+                arrays[name], arrays[name + "_rows"] = a[rows], rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def valu_bound(engine, kernel_avg_s, clock_mhz=None):
@@ -433,6 +477,8 @@ def main():
     args = parse()
     if args.repeats <= 0:
         args.repeats = max(9, -(-1000 // max(args.steps, 1)))
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     # torchrun sets these before this process touches the GPU; nothing below re-executes the process
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -502,49 +548,22 @@ def main():
         return spec, eng, run, {"synthetic_data_s": round(t1 - t0, 3), "engine_setup_s": round(t2 - t1, 3)}
 
     spec, eng, run, setup = build(args.mode)
-    clock_before = eng.device_clock_mhz()
-    times = time_steps(run, args.steps, args.warmup, dist_on, device, args.repeats)
-    clock_after = eng.device_clock_mhz()
-    dt = median(times)
+    clock_before = eng.device_clock_mhz() if args.full else None
+    dt = time_steps(run, args.steps, args.warmup, dist_on, device)[0]
     sps = args.steps / dt
+    n_timed = args.warmup + args.steps                       # steps run up to the end of the headline region
+    outputs = step_outputs(eng, run, dist_on) if args.dump_outputs else None
+    if outputs is not None and rank == 0:
+        dump_outputs(outputs, args.dump_outputs)
     losses = run.perf_losses()
     ok, first_bad, n_bad = eng.status()
-    n_timed = args.warmup + args.steps * len(times)          # steps run up to the end of the last timed region
-    roof = kernel_roofline(eng, run, args.roofline_launches, dt / args.steps)
-    if dist_on:
-        roof["note"] = f"per-rank kernel on {eng.Nc_local} of {args.cells} cells"
-    # "loss read back each step unless stated" -- the headline keeps the losses on the device and reads them
-    # once at the end; this is the same step with the loss copied to the host after every step
-    t0 = time.perf_counter()
-    nrb = 100
-    for _ in range(nrb):
-        run.run_perf(1, sync=False)
-        float(run.loss_hist[run.step_idx - 1].item())
-    rb_sps = nrb / (time.perf_counter() - t0)
-    # ... and with the loss ring in pinned host memory, written by the device and polled by the host (what fit() does when
-    # it has to look at every loss: early_exit / store_output); single-rank fused path
-    rb_host = None
-    if not dist_on and not solo_group and run.adam_impl == "fused3" and not run.use_graph:
-        run.step_with_loss()
-        t0 = time.perf_counter()
-        ls = [run.step_with_loss() for _ in range(nrb)]
-        rb_host = nrb / (time.perf_counter() - t0)
-        assert all(l == l for l in ls) or n_bad > 0
     out = {
         "metric": baseline_metric() if args.mode != "phase" else "SVI steps/sec, phase_inference",
         "value": round(sps, 2), "unit": "SVI steps/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "repeats": len(times), "repeat_ms_per_step": [round(1e3 * t / args.steps, 4) for t in times],
-        "ms_per_step_min_max": [round(1e3 * min(times) / args.steps, 4), round(1e3 * max(times) / args.steps, 4)],
-        "timing": "value / ms_per_step = MEDIAN of `repeats` timed regions of exactly `steps` steps each (barrier + "
-                  "synchronize on both sides, max over ranks); repeat_ms_per_step lists all of them in order",
-        "device_clock_mhz": {"before_timed_region": round(clock_before, 1), "after_timed_region": round(clock_after, 1),
-                             "method": "shader clock: s_memtime ticks per 200 us of s_memrealtime, one wave "
-                                       "(vc_device_clock_mhz) -- the clock of a LIGHT kernel; the sustained clock inside the "
-                                       "likelihood kernel is lower (2.29-2.36 GHz at steady state, 1.6-1.7 GHz during the first "
-                                       "~30 ms of a fresh process: profiles/r02_wave_timeline_u16.txt), and that ramp shows in "
-                                       "the first entries of repeat_ms_per_step"},
+        "timing": "value / ms_per_step = ONE timed region of exactly `steps` steps after `warmup` untimed ones (barrier + "
+                  "synchronize on both sides, max over ranks)",
         "setup_s": setup,
         "config": {"workload": f"synthetic {args.cells} cells x {args.genes} genes " + ("phase_inference" if args.mode == "phase" else "velocity_inference") + ", "
                                + {"vjoint": "mean-field guide, nothing conditioned (every gradient)",
@@ -562,15 +581,54 @@ def main():
                                                                             + (f" [{run.exchange}]" if run.exchange else "") + " -> " if (dist_on or solo_group) else "")
                             + f"ClippedAdam ({run.adam_impl}), " + ("hipGraph replay" if run.use_graph else "eager launches")
                             + "; losses stay in a device ring and are read back ONCE after the timed region "
-                              "(with_loss_readback_each_step gives the rate with a host read-back after every step)")},
-        "with_loss_readback_each_step": {"value": round(rb_host if rb_host else rb_sps, 2), "unit": "SVI steps/s", "steps": nrb,
-                                         "how": ("loss ring in pinned host memory, written by the device, polled by the host "
-                                                 "(SVIRunner.step_with_loss)" if rb_host else "stream synchronise + copy of the loss"),
-                                         "by_sync_and_copy": round(rb_sps, 2)},
-        "roofline": roof,
+                              "(--full: with_loss_readback_each_step gives the rate with a host read-back after every step)")},
         "loss_first_last": [losses[0], losses[n_timed - 1]],
         "nonfinite_loss_steps": n_bad,
     }
+    if args.dump_outputs:
+        out["outputs"] = {"dir": args.dump_outputs, "arrays": sorted(outputs),
+                          "what": "guide parameters (unconstrained) and the loss after the last timed step"}
+    if args.full:
+        # further regions of the same step: the spread the headline's one region does not show
+        times = time_steps(run, args.steps, 0, dist_on, device, args.repeats)
+        clock_after = eng.device_clock_mhz()
+        out["repeats"] = len(times)
+        out["repeat_ms_per_step"] = [round(1e3 * t / args.steps, 4) for t in times]
+        out["ms_per_step_median_of_repeats"] = round(1e3 * median(times) / args.steps, 4)
+        out["ms_per_step_min_max"] = [round(1e3 * min(times) / args.steps, 4), round(1e3 * max(times) / args.steps, 4)]
+        out["timing"] += ("; repeat_ms_per_step: `repeats` further regions of `steps` steps each, timed right after it, in "
+                          "order, and their median")
+        out["device_clock_mhz"] = {"before_timed_region": round(clock_before, 1), "after_timed_region": round(clock_after, 1),
+                                   "method": "shader clock: s_memtime ticks per 200 us of s_memrealtime, one wave "
+                                             "(vc_device_clock_mhz) -- the clock of a LIGHT kernel; the sustained clock inside the "
+                                             "likelihood kernel is lower (2.29-2.36 GHz at steady state, 1.6-1.7 GHz during the first "
+                                             "~30 ms of a fresh process: profiles/r02_wave_timeline_u16.txt), and that ramp shows in "
+                                             "the first entries of repeat_ms_per_step"}
+        roof = kernel_roofline(eng, run, args.roofline_launches, median(times) / args.steps)
+        if dist_on:
+            roof["note"] = f"per-rank kernel on {eng.Nc_local} of {args.cells} cells"
+        # "loss read back each step unless stated" -- the headline keeps the losses on the device and reads them
+        # once at the end; this is the same step with the loss copied to the host after every step
+        t0 = time.perf_counter()
+        nrb = 100
+        for _ in range(nrb):
+            run.run_perf(1, sync=False)
+            float(run.loss_hist[run.step_idx - 1].item())
+        rb_sps = nrb / (time.perf_counter() - t0)
+        # ... and with the loss ring in pinned host memory, written by the device and polled by the host (what fit() does when
+        # it has to look at every loss: early_exit / store_output); single-rank fused path
+        rb_host = None
+        if not dist_on and not solo_group and run.adam_impl == "fused3" and not run.use_graph:
+            run.step_with_loss()
+            t0 = time.perf_counter()
+            ls = [run.step_with_loss() for _ in range(nrb)]
+            rb_host = nrb / (time.perf_counter() - t0)
+            assert all(l == l for l in ls) or n_bad > 0
+        out["with_loss_readback_each_step"] = {"value": round(rb_host if rb_host else rb_sps, 2), "unit": "SVI steps/s", "steps": nrb,
+                                               "how": ("loss ring in pinned host memory, written by the device, polled by the host "
+                                                       "(SVIRunner.step_with_loss)" if rb_host else "stream synchronise + copy of the loss"),
+                                               "by_sync_and_copy": round(rb_sps, 2)}
+        out["roofline"] = roof
     if dist_on or solo_group:
         import torch.distributed as dist
         me = dict(device_identity(device), rank=rank, local_rank=local_rank, cells=eng.Nc_local, pid=os.getpid())
@@ -583,7 +641,7 @@ def main():
                               "exchange_check": getattr(run, "exchange_check", None)}
     else:
         out["device"] = device_identity(device)
-    if dist_on and not args.no_weak:
+    if args.full and dist_on and not args.no_weak:
         # Weak scaling from the same invocation: --cells cells PER RANK (N x the strong problem), the same
         # kernels and the same exchange; the strong run above stays the headline (the north-star target is phrased on the fixed
         # 50k x 2k problem), this block says what a rank's step costs when its shard does not shrink with N.
@@ -621,9 +679,9 @@ def main():
             return {"error": str(ex)[:200]}
 
     extra = {}
-    if not dist_on and not solo_group and not args.no_loss_every_demo and rank == 0:
+    if args.full and not dist_on and not solo_group and not args.no_loss_every_demo and rank == 0:
         out["opt_in_loss_every_10"] = loss_every_demo(eng)
-    if not args.no_extra_modes and not dist_on:
+    if args.full and not args.no_extra_modes and not dist_on:
         del run, eng, spec
         torch.cuda.empty_cache()
         for m in [x for x in ("vcond", "phase", "vjoint") if x != args.mode][:2]:
@@ -665,7 +723,7 @@ def main():
             del s2, e2, r2
             torch.cuda.empty_cache()
         out["modes"] = extra
-    if rank == 0 and not dist_on and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not dist_on and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, args.mode, device)
         out["elbo_match_full"] = out["cpu_baseline"].get("elbo_match_full")     # the metric's second half, at the quoted size
     if dist_on or solo_group:

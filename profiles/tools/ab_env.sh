@@ -9,7 +9,7 @@ for ent in "$@"; do
   for rep in 1 2; do for s in ${sets//,/ }; do
     tag="${s//[^A-Za-z0-9_]/_}"
     ( if [ "$s" != "-" ]; then for kv in ${s//+/ }; do export "$kv"; done; fi
-      python bench.py --steps ${STEPS:-100} --warmup 20 --repeats 5 --no-cpu-baseline --no-extra-modes --mode $mode ${BENCH_ARGS} > $out/${mode}_${tag}_$rep.json 2> $out/${mode}_${tag}_$rep.err )
+      python bench.py --steps ${STEPS:-100} --warmup 20 --full --repeats 5 --no-cpu-baseline --no-extra-modes --mode $mode ${BENCH_ARGS} > $out/${mode}_${tag}_$rep.json 2> $out/${mode}_${tag}_$rep.err )
     python - <<PY
 import json
 try:

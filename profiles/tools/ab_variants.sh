@@ -8,7 +8,7 @@ mkdir -p $out
 for ent in "$@"; do
   mode="${ent%%:*}"; libs="${ent#*:}"
   for rep in 1 2; do for lib in ${libs//,/ }; do
-    VC_LIB_PATH=$PWD/scratch/libs/$lib.so python bench.py --steps ${STEPS:-100} --warmup 20 --repeats 5 --no-cpu-baseline --no-extra-modes --mode $mode ${BENCH_ARGS} > $out/${mode}_${lib}_$rep.json 2> $out/${mode}_${lib}_$rep.err
+    VC_LIB_PATH=$PWD/scratch/libs/$lib.so python bench.py --steps ${STEPS:-100} --warmup 20 --full --repeats 5 --no-cpu-baseline --no-extra-modes --mode $mode ${BENCH_ARGS} > $out/${mode}_${lib}_$rep.json 2> $out/${mode}_${lib}_$rep.err
     python - <<PY
 import json
 try:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """The roofline of the bench line reproduced from the rocprofv3 kernel trace of THE SAME PROCESS (VERDICT r5 hygiene #10 / item 7).
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/<tag>_stats -- python3 bench.py ... > <tag>/bench_under_rocprof.json
-    python profiles/tools/roofline_from_trace.py gpurun_out/<tag>_stats <tag>/bench_under_rocprof.json <tag>/roofline_check.txt
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUTDIR/<tag>_stats -- python3 bench.py --full ... > <tag>/bench_under_rocprof.json
+    python profiles/tools/roofline_from_trace.py OUTDIR/<tag>_stats <tag>/bench_under_rocprof.json <tag>/roofline_check.txt
 
 bench.py measures `roofline.kernel_avg_us` with hipEvents over `roofline.launches` (100) eager steps of the headline mode, bracketed by
 two launches of the library's clock-probe kernel (`vc_device_clock_mhz`: before = `device_clock_mhz.after_timed_region`, after = the
