@@ -169,7 +169,48 @@ static void batch_case(long long Nc, int Nb, int nGB, int n_cu, int bpc, bool sh
   }
 }
 
+// the condition of every batch (vc_batch_conditions): D is (Nx, Nc) row-major, bid the batch of every cell
+static void condition_cases() {
+  std::vector<int> cond;
+  // one condition per batch: batches 0 and 2 in condition 1, batch 1 in condition 0
+  {
+    const std::vector<int> bid = {0, 1, 2, 0, 1, 2};
+    const std::vector<float> D = {0, 1, 0, 0, 1, 0,
+                                  1, 0, 1, 1, 0, 1};
+    CHECK(vc_batch_conditions(D.data(), 2, 6, bid, 3, cond));
+    CHECK((cond == std::vector<int>{1, 0, 1}));
+  }
+  // a batch that mixes conditions: cells 0 and 2 are both batch 0, in conditions 0 and 1
+  {
+    const std::vector<int> bid = {0, 1, 0};
+    const std::vector<float> D = {1, 1, 0,
+                                  0, 0, 1};
+    CHECK(!vc_batch_conditions(D.data(), 2, 3, bid, 2, cond));
+    CHECK(cond.empty());
+  }
+  // D not one-hot: a fractional entry, a cell in two conditions, a cell in none
+  {
+    const std::vector<int> bid = {0, 1};
+    const std::vector<float> frac = {0.5f, 1, 0.5f, 0}, both = {1, 1, 1, 0}, none = {0, 1, 0, 0};
+    for (const auto* D : {&frac, &both, &none}) {
+      CHECK(!vc_batch_conditions(D->data(), 2, 2, bid, 2, cond));
+      CHECK(cond.empty());
+    }
+    CHECK(!vc_batch_conditions(frac.data(), 0, 2, bid, 2, cond));      // no condition rows at all
+  }
+  // a batch with no cells on this rank: condition 0
+  {
+    const std::vector<int> bid = {0, 2, 2};
+    const std::vector<float> D = {0, 0, 0,
+                                  0, 1, 1,
+                                  1, 0, 0};
+    CHECK(vc_batch_conditions(D.data(), 3, 3, bid, 3, cond));
+    CHECK((cond == std::vector<int>{2, 0, 1}));
+  }
+}
+
 int main() {
+  condition_cases();
   {
     std::mt19937 rng(5);
     for (int it = 0; it < 120; ++it)

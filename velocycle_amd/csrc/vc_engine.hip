@@ -140,7 +140,6 @@ struct vc_engine {
   // vc_set_loss_every: the gradient-only instantiation of the U-only kernel (null: none for this configuration), the period and
   // the count of likelihood launches of the fused single-rank runs since it was set (launch n evaluates the loss iff n % k == 0)
   vc_main_launch_fn main_fn_nl = nullptr;
-  const char* main_name_nl = "";
   int loss_every = 1;
   long long loss_ctr = 0;
   vc_main_launch_fn phase_fn = nullptr;  // S-only kernel used once to hoist the S term (VU kind)
@@ -148,6 +147,7 @@ struct vc_engine {
   long long gs = 0, cs = 0;          // strides of the host copies hS / hU
   long long dgs = 0, dcs = 0;        // strides of the dense device sources
   bool hist_each_step = false;
+  int tail_kind = 0;                   // which launch follows K_main in vc_svi_run_fused's steady state (vc_finalize: choose_tail_kind)
   // tutorial flow: ordinary (three-launch) fused steps since the tables were last primed; from the third on the merged tail
   // launch may be used (both halves of the loss terms K_tail's cell blocks write are then in place)
   int plain_steps = 0;
@@ -236,7 +236,6 @@ struct vc_engine {
   }
 
 static bool cond(const vc_engine* e, int site) { return (e->d.cond >> site) & 1u; }
-static int fused_tail_kind(const vc_engine* e);
 
 static long long site_size(const vc_engine* e, int site) {
   const VcDims& d = e->d;
@@ -668,439 +667,468 @@ extern "C" int vc_finalize(vc_engine* e, void* hip_stream) {
   return rc;
 }
 
-static int finalize_impl(vc_engine* e, void* hip_stream) {
+// ---------------------------------------------------------------------------------------------
+// vc_finalize, stage by stage (finalize_impl).  Every stage reads and writes e->d / e->b as the steps will see them; what a stage
+// hands to a later one besides that travels in FinalizeState.
+
+static const unsigned OVF_CAP = 1u << 22;      // overflow entries per matrix of the device histogram pass
+
+// vc_finalize's set-up scratch: the device histogram tables and overflow lists of the count pass, and its flag words.  These are
+// not engine allocations (vc_destroy does not see them): whatever is still held when finalize_impl returns, by any path, or
+// unwinds is freed here.
+struct SetupScratch {
+  unsigned* tab[2] = {nullptr, nullptr};
+  float* ovf_val[2] = {nullptr, nullptr};
+  int* ovf_gene[2] = {nullptr, nullptr};
+  unsigned* ovf_n = nullptr;
+  int* bad = nullptr;
+  size_t bytes = 0;                     // allocated so far (part of vc_stats.setup_transient_bytes)
+  SetupScratch() = default;
+  SetupScratch(const SetupScratch&) = delete;
+  SetupScratch& operator=(const SetupScratch&) = delete;
+  ~SetupScratch() { release(); }
+  template <class T>
+  int alloc(vc_engine* e, T** p, size_t n) {
+    hipError_t er = hipMalloc((void**)p, n * sizeof(T));
+    if (er != hipSuccess) return e->fail(VC_ERR_HIP, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(er));
+    bytes += n * sizeof(T);
+    return VC_OK;
+  }
+  template <class T>
+  static void drop(T*& p) { if (p) (void)hipFree(p); p = nullptr; }
+  void release() {
+    for (int m = 0; m < 2; ++m) { drop(tab[m]); drop(ovf_val[m]); drop(ovf_gene[m]); }
+    drop(ovf_n); drop(bad);
+  }
+};
+
+struct FinalizeState {
+  hipStream_t st = nullptr;
+  std::vector<int> bat_id, bat_pos, bat_ord, bat_len;   // one-hot batches: batch of every cell, vc_order_by_batch of them
+  bool bat_sorted = true;                               // ... the cells are in batch order already
+  int n_cu = 256;                                        // the device: compute units and the LDS a workgroup may ask for
+  size_t lds_cap = 0;
+  const void* main_kernel = nullptr;                     // code object of the selected likelihood kernel
+  const int* dev_ord = nullptr;                          // cells in batch order (count pass; freed behind the tiling)
+  bool want_hist = false, dev_hist = false;              // count histograms needed / built on the device
+  SetupScratch scratch;
+  size_t transient = 0;                                  // other set-up bytes: consumed count sources, the float32 layout
+  double lg_S = 0.0, lg_U = 0.0;                         // sum lgamma(k + 1)
+};
+
+static int nq_of(const VcDims& d, int kind) { return kind == VC_KIND_PHASE ? d.Kq + 1 : (kind == VC_KIND_VFULL ? d.Kq + 3 : 2); }
+
+// the instantiation (H, NB, kind, noise of d; gpl; variant = count storage | 2 gradient-only | 4 PWL) if it is compiled and runs
+// without scratch -- asm-issued count loads: a spilled destination tuple would be stored before its data has landed
+static vc_main_launch_fn find_main_noscratch(const VcDims& d, int gpl, int variant, const void** kernel) {
+  const void* k = nullptr;
+  hipFuncAttributes fa;
+  vc_main_launch_fn fn = vc_find_main_kernel(d.H, d.nbk, d.kind, d.noise, gpl, variant, nullptr, &k);
+  if (!fn || !k || hipFuncGetAttributes(&fa, k) != hipSuccess || fa.localSizeBytes > 0) return nullptr;
+  if (kernel) *kernel = k;
+  return fn;
+}
+
+// Which launch follows K_main in the steady state of vc_svi_run_fused: 1 = the tutorial flow's merged tail (vc_launch_tail_merged),
+// 2 = the one-launch tail of every other single-rank step that has what it needs (vc_launch_tail2), 0 = K_tail + K_omega
+static int choose_tail_kind(const vc_engine* e) {
+  if (e->d.generic) return 0;
+  const bool with_hist = e->hist_each_step;
+  bool merged = e->d.pw_inline && e->d.kind == VC_KIND_VU && !with_hist && (e->d.cond >> VC_SITE_PHIXY & 1u);
+  if (e->tun.no_tail_merged) merged = false;
+  if (merged) return 1;
+  // Round 4: every other single-rank step in TWO launches as well -- the phase model (no nu_omega chain), and the velocity
+  // models whenever K_main supplies the partials of d loglik / d nu_omega itself (pw_inline), so that the chain runs inside the
+  // cell blocks.  tuning.no_tail2 keeps the three-launch step (A/B, tests: the same bits).
+  bool tail2 = e->cfg.world_size == 1 && (e->d.model == VC_MODEL_PHASE || e->d.pw_inline != 0);
+  if (e->tun.no_tail2) tail2 = false;
+  return tail2 ? 2 : 0;
+}
+
+static int fin_check_inputs(vc_engine* e) {
   if (e->finalized) return e->fail(VC_ERR_STATE, "vc_finalize called twice");
   if (!e->have_counts || !e->have_cells) return e->fail(VC_ERR_STATE, "vc_finalize: counts / cell data not set");
-  hipStream_t st = (hipStream_t)hip_stream;
-  VcDims& d = e->d;
-  VcBufs& b = e->b;
+  const VcDims& d = e->d;
   const bool vel = d.model == VC_MODEL_VELOCITY;
-  const bool lrmn = vel && d.guide == VC_GUIDE_LRMN;
-  const bool nb = d.noise == VC_NOISE_NB;
   // required priors
-  const int need_all[] = {VC_PRIOR_MU_NU, VC_PRIOR_SD_NU};
-  for (int w : need_all)
+  for (int w : {VC_PRIOR_MU_NU, VC_PRIOR_SD_NU})
     if (!e->prior_set[w]) return e->fail(VC_ERR_STATE, "vc_finalize: prior %d not set", w);
   if (vel)
     for (int w = VC_PRIOR_MU_GAMMA; w <= VC_PRIOR_SD_NUOMEGA; ++w)
       if (!e->prior_set[w]) return e->fail(VC_ERR_STATE, "vc_finalize: prior %d not set", w);
   if (!vel && d.with_dnu && !e->prior_set[VC_PRIOR_SD_DNU])
     return e->fail(VC_ERR_STATE, "vc_finalize: sd_dnu prior not set");
-  e->finalize_started = true;
+  return VC_OK;
+}
 
-  // Batch offsets.  The reference's design matrix is one-hot by construction (make_design_matrix, preprocessing.py:65-93): then the
-  // offset of a cell's batch is folded into the constant harmonic per workgroup of the likelihood kernel (cells ordered by batch,
-  // workgroups aligned to the batch boundaries), the kernel without batch terms runs for ANY number of batches and the gradient
-  // of an offset is a sum over its batch's workgroups.  Any other matrix keeps the dense contraction (<= VC_MAXNB batches on the
-  // fast kernel set, the run-time-sized set beyond).
-  std::vector<int> bat_id, bat_pos, bat_ord, bat_len;
-  bool bat_sorted = true;
+// Batch offsets.  The reference's design matrix is one-hot by construction (make_design_matrix, preprocessing.py:65-93): then the
+// offset of a cell's batch is folded into the constant harmonic per workgroup of the likelihood kernel (cells ordered by batch,
+// workgroups aligned to the batch boundaries), the kernel without batch terms runs for ANY number of batches and the gradient
+// of an offset is a sum over its batch's workgroups.  Any other matrix keeps the dense contraction (<= VC_MAXNB batches on the
+// fast kernel set, the run-time-sized set beyond).
+static void fin_batch_plan(vc_engine* e, FinalizeState& s) {
+  VcDims& d = e->d;
+  const bool vel = d.model == VC_MODEL_VELOCITY;
   d.onehot = 0;
   if (d.with_dnu && d.Nb >= 1 && !e->tun.dense_batches && !e->tun.force_generic && !e->generic_needed &&
-      vc_onehot_batches(e->hDb.data(), d.Nb, d.Nc, bat_id)) {
+      vc_onehot_batches(e->hDb.data(), d.Nb, d.Nc, s.bat_id)) {
     d.onehot = 1;
-    bat_sorted = vc_order_by_batch(bat_id, d.Nb, bat_pos, bat_ord, bat_len);
+    s.bat_sorted = vc_order_by_batch(s.bat_id, d.Nb, s.bat_pos, s.bat_ord, s.bat_len);
     // the condition design D (Nx, Nc) is one-hot and CONSTANT within every batch (the tutorials pass the same matrix for both:
     // Tutorial_Aissa_PC9_TwoSample cell 40)?  Then every workgroup of the likelihood kernel lies inside one condition too.
-    e->bat_cond.assign((size_t)d.Nb, -1);
-    bool okc = vel && d.Nx >= 1 && e->hD.size() == (size_t)d.Nx * d.Nc;
-    for (long long c = 0; c < (long long)d.Nc && okc; ++c) {
-      int xc = -1;
-      for (int x = 0; x < d.Nx; ++x) {
-        const float v = e->hD[(size_t)x * d.Nc + c];
-        if (v == 1.f && xc < 0) xc = x;
-        else if (v != 0.f) okc = false;
-      }
-      if (xc < 0) okc = false;
-      int& bc = e->bat_cond[(size_t)bat_id[(size_t)c]];
-      if (bc < 0) bc = xc;
-      else if (bc != xc) okc = false;
-    }
-    for (int& v : e->bat_cond) if (v < 0) v = 0;       // (a batch without cells on this rank)
-    if (!okc) e->bat_cond.clear();
+    e->bat_cond.clear();
+    if (vel && e->hD.size() == (size_t)d.Nx * d.Nc) vc_batch_conditions(e->hD.data(), d.Nx, d.Nc, s.bat_id, d.Nb, e->bat_cond);
   }
   d.generic = (e->tun.force_generic || e->generic_needed || (e->generic_nb && !d.onehot)) ? 1 : 0;
   d.Kq = d.onehot ? d.Nh : d.K;
-  d.nbk = d.onehot ? 0 : d.Nb;
-  const int knb = d.nbk;            // the NB template argument of the likelihood kernel
-  // kernel kind
+  d.nbk = d.onehot ? 0 : d.Nb;          // the NB template argument of the likelihood kernel
+}
+
+// Kernel kind, genes per lane, the likelihood kernel (and the S-only kernel of the hoisted term); reads the device once
+static int fin_choose_kernel(vc_engine* e, FinalizeState& s) {
+  VcDims& d = e->d;
+  const bool vel = d.model == VC_MODEL_VELOCITY;
+  const bool nb = d.noise == VC_NOISE_NB;
+  const int knb = d.nbk;
   if (!vel) d.kind = VC_KIND_PHASE;
   else {
     const bool vu = cond(e, VC_SITE_PHIXY) && cond(e, VC_SITE_NU) && (!d.with_dnu || cond(e, VC_SITE_DNU)) &&
                     (!nb || cond(e, VC_SITE_SHAPE_INV));
     d.kind = vu ? VC_KIND_VU : VC_KIND_VFULL;
   }
-  auto nq_of = [&](int kind) { return kind == VC_KIND_PHASE ? d.Kq + 1 : (kind == VC_KIND_VFULL ? d.Kq + 3 : 2); };
-  auto nco_of = [&](int kind) { return kind == VC_KIND_VFULL ? 3 : 1; };
-  d.nq = nq_of(d.kind);
-  d.nco = nco_of(d.kind);
+  d.nq = nq_of(d, d.kind);
+  d.nco = d.kind == VC_KIND_VFULL ? 3 : 1;
+  {
+    hipDeviceProp_t prop;
+    int dev = 0;
+    HIPCHK(e, hipGetDevice(&dev));
+    HIPCHK(e, hipGetDeviceProperties(&prop, dev));
+    if (prop.multiProcessorCount > 0) s.n_cu = prop.multiProcessorCount;
+    s.lds_cap = std::max<size_t>(prop.sharedMemPerBlockOptin, prop.maxSharedMemoryPerMultiProcessor);
+  }
   // genes per lane: 8 amortises the per-cell work over twice the genes and is chosen whenever that instantiation's
   // per-gene state (latents + accumulators) fits 2 waves per SIMD without scratch, which the code object itself
   // tells (private segment size 0); else 4.
   d.gpl = d.generic ? 2 : 4;
-  const size_t max_scratch = 0;      // asm-issued count loads: a spilled destination tuple would be stored before its data has landed
-  if (!d.generic) {
-    const void* k8 = nullptr;
-    hipFuncAttributes fa;
-    if (vc_find_main_kernel(d.H, knb, d.kind, d.noise, 8, 0, nullptr, &k8) && k8 &&
-        hipFuncGetAttributes(&fa, k8) == hipSuccess && fa.localSizeBytes <= max_scratch)
-      d.gpl = 8;
-    if (d.gpl == 8) {
-      // Small shards (round 3, profiles/r03_small_shard.md): with few cells per wave the per-wave prologue / epilogue of the
-      // 8-genes-per-lane kernel (twice the gene-table loads, twice the rows to combine) outweighs what it saves per cell --
-      // 6 250 cells x 2 000 genes: 22.5 vs 24.7 us (S+U), 16.8 vs 17.8 (U only); 12 500: 35.6 vs 36.8 (S+U) but 26.1 vs 23.7
-      // (U only); 25 000: 61.7 vs 62.9; 50 000: 8 genes per lane wins.  Decided from the cells a wave would get under the
-      // 8-genes-per-lane tiling -- a pure function of (cells, genes, kernel kind, occupancy, CUs), like the tiling itself.
-      int bpc8 = 0, n_cu = 256, dev = 0;
-      hipDeviceProp_t prop;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc8, k8, 256, 0) == hipSuccess && bpc8 >= 1 &&
-          hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) {
-        if (prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-        const int ngb8 = (d.Ng + 511) / 512;
-        // decided from a RANK-INVARIANT cell count (the largest balanced shard): balanced shards differ by one cell, and two
-        // ranks on opposite sides of the threshold would disagree on Ng_pad -- and with it on the exchange buffer's layout
-        const long long world = e->cfg.world_size, ncg = e->cfg.Nc_global > 0 ? e->cfg.Nc_global : d.Nc;
-        const int shard_cells = world > 1 ? (int)((ncg + world - 1) / world) : d.Nc;
-        const VcTiling t8 = vc_tile_cells(shard_cells, ngb8, n_cu, bpc8, VC_WAVES, 0, nullptr, 12);
-        const int small_cw = d.kind == VC_KIND_VFULL ? 52 : 10;
-        // Round 4, S+U kernel on ONE rank: the 8-genes-per-lane kernel can emit the nu_omega partials itself (room in the LDS),
-        // which makes the step two launches instead of three; the 4-genes-per-lane kernel can do that only where a wave has
-        // <= 12 cells (its reduction tiles fill the LDS: profiles/r04_small_shard.md).  Measured at 2 000 genes, 6 250 ... 20 000
-        // cells: K_main + 4-5 us, the step - 1.3 ... - 3.4 us (- 3 ... - 7 %); equal at 25 000.  So: 4 genes per lane only where
-        // that kernel keeps the step at two launches as well.
-        bool two_launch8 = false;
-        if (d.kind == VC_KIND_VFULL && world == 1 && VC_PW_INLINE && d.NW >= 1 && d.NW <= VC_PWQ) {
-          const void* k4 = nullptr;
-          int bpc4 = 0;
-          if (e->tun.pw_inline != 1 && !e->tun.no_tail2 &&
-              vc_find_main_kernel(d.H, knb, d.kind, d.noise, 4, 0, nullptr, &k4) && k4 &&
-              hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc4, k4, 256, 0) == hipSuccess && bpc4 >= 1) {
-            const VcTiling t4 = vc_tile_cells(shard_cells, (d.Ng + 255) / 256, n_cu, bpc4, VC_WAVES, 0, nullptr, 12);
-            two_launch8 = t4.cw > 12;
-          }
+  const void* k8 = nullptr;
+  if (!d.generic && find_main_noscratch(d, 8, 0, &k8)) {
+    d.gpl = 8;
+    // Small shards (round 3, profiles/r03_small_shard.md): with few cells per wave the per-wave prologue / epilogue of the
+    // 8-genes-per-lane kernel (twice the gene-table loads, twice the rows to combine) outweighs what it saves per cell --
+    // 6 250 cells x 2 000 genes: 22.5 vs 24.7 us (S+U), 16.8 vs 17.8 (U only); 12 500: 35.6 vs 36.8 (S+U) but 26.1 vs 23.7
+    // (U only); 25 000: 61.7 vs 62.9; 50 000: 8 genes per lane wins.  Decided from the cells a wave would get under the
+    // 8-genes-per-lane tiling -- a pure function of (cells, genes, kernel kind, occupancy, CUs), like the tiling itself.
+    int bpc8 = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc8, k8, 256, 0) == hipSuccess && bpc8 >= 1) {
+      const int ngb8 = (d.Ng + 511) / 512;
+      // decided from a RANK-INVARIANT cell count (the largest balanced shard): balanced shards differ by one cell, and two
+      // ranks on opposite sides of the threshold would disagree on Ng_pad -- and with it on the exchange buffer's layout
+      const long long world = e->cfg.world_size, ncg = e->cfg.Nc_global > 0 ? e->cfg.Nc_global : d.Nc;
+      const int shard_cells = world > 1 ? (int)((ncg + world - 1) / world) : d.Nc;
+      const VcTiling t8 = vc_tile_cells(shard_cells, ngb8, s.n_cu, bpc8, VC_WAVES, 0, nullptr, 12);
+      const int small_cw = d.kind == VC_KIND_VFULL ? 52 : 10;
+      // Round 4, S+U kernel on ONE rank: the 8-genes-per-lane kernel can emit the nu_omega partials itself (room in the LDS),
+      // which makes the step two launches instead of three; the 4-genes-per-lane kernel can do that only where a wave has
+      // <= 12 cells (its reduction tiles fill the LDS: profiles/r04_small_shard.md).  Measured at 2 000 genes, 6 250 ... 20 000
+      // cells: K_main + 4-5 us, the step - 1.3 ... - 3.4 us (- 3 ... - 7 %); equal at 25 000.  So: 4 genes per lane only where
+      // that kernel keeps the step at two launches as well.
+      bool two_launch8 = false;
+      if (d.kind == VC_KIND_VFULL && world == 1 && VC_PW_INLINE && d.NW >= 1 && d.NW <= VC_PWQ) {
+        const void* k4 = nullptr;
+        int bpc4 = 0;
+        if (e->tun.pw_inline != 1 && !e->tun.no_tail2 &&
+            vc_find_main_kernel(d.H, knb, d.kind, d.noise, 4, 0, nullptr, &k4) && k4 &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc4, k4, 256, 0) == hipSuccess && bpc4 >= 1) {
+          const VcTiling t4 = vc_tile_cells(shard_cells, (d.Ng + 255) / 256, s.n_cu, bpc4, VC_WAVES, 0, nullptr, 12);
+          two_launch8 = t4.cw > 12;
         }
-        if (t8.cw <= small_cw && !two_launch8) d.gpl = 4;
       }
+      if (t8.cw <= small_cw && !two_launch8) d.gpl = 4;
     }
   }
-  if (!d.generic && e->tun.genes_per_lane) {
-    if (e->tun.genes_per_lane == 4) d.gpl = 4;
-    if (e->tun.genes_per_lane == 8) {       // honoured only where the 8-genes-per-lane kernel may run at all (no scratch: see above)
-      const void* k8 = nullptr;
-      hipFuncAttributes fa;
-      if (vc_find_main_kernel(d.H, knb, d.kind, d.noise, 8, 0, nullptr, &k8) && k8 &&
-          hipFuncGetAttributes(&fa, k8) == hipSuccess && fa.localSizeBytes <= max_scratch)
-        d.gpl = 8;
-    }
-  }
+  if (!d.generic && e->tun.genes_per_lane == 4) d.gpl = 4;
+  // (8 is honoured only where the 8-genes-per-lane kernel may run at all: no scratch, see above)
+  if (!d.generic && e->tun.genes_per_lane == 8 && find_main_noscratch(d, 8, 0, nullptr)) d.gpl = 8;
   d.gbw = 64 * d.gpl;
   d.nGB = (d.Ng + d.gbw - 1) / d.gbw;
   d.Ng_pad = d.nGB * d.gbw;
-  const void* main_kernel = nullptr;
   d.c16 = 0;
   if (d.generic) {
     // the run-time-sized set: one wave per workgroup, 2 genes per lane (gene blocks of 128), float32 counts
     static const char* gen_names[3][3] = {{"generic_phase_nb", "generic_phase_poisson", "generic_phase_lognormal"},
                                           {"generic_vfull_nb", "generic_vfull_poisson", "generic_vfull_lognormal"},
                                           {"generic_vu_nb", "generic_vu_poisson", "generic_vu_lognormal"}};
-    e->main_fn = vc_find_generic_main_kernel(d.kind, d.noise, &main_kernel);
+    e->main_fn = vc_find_generic_main_kernel(d.kind, d.noise, &s.main_kernel);
     e->main_name = gen_names[d.kind][d.noise];
     if (d.kind == VC_KIND_VU) e->phase_fn = vc_find_generic_main_kernel(VC_KIND_PHASE, d.noise, nullptr);
   } else {
-    e->main_fn = vc_find_main_kernel(d.H, knb, d.kind, d.noise, d.gpl, 0, &e->main_name, &main_kernel);
+    e->main_fn = vc_find_main_kernel(d.H, knb, d.kind, d.noise, d.gpl, 0, &e->main_name, &s.main_kernel);
   }
   if (!e->main_fn) return e->fail(VC_ERR_UNSUPPORTED, "no likelihood kernel for H=%d Nb=%d kind=%d noise=%d", d.H, knb, d.kind, d.noise);
   if (d.kind == VC_KIND_VU && !d.generic) {
     e->phase_fn = vc_find_main_kernel(d.H, knb, VC_KIND_PHASE, d.noise, d.gpl, 0, nullptr, nullptr);
     if (!e->phase_fn) return e->fail(VC_ERR_UNSUPPORTED, "no S-only kernel for the hoisted term");
   }
-  // HBM layout of the counts: [gene block][cell][gbw], zero padded in genes; the per-gene count histograms are built on
-  // the device in the same pass (dense bins + overflow list), so that no dense matrix crosses back to the host
-  const bool want_hist = d.noise != VC_NOISE_LOGNORMAL;
-  const bool dev_hist = want_hist && !e->host_hist;
-  const unsigned OVF_CAP = 1u << 22;
-  unsigned* tab[2] = {nullptr, nullptr};
-  float* ovf_val[2] = {nullptr, nullptr};
-  int* ovf_gene[2] = {nullptr, nullptr};
-  unsigned* ovf_n = nullptr;
-  int* bad = nullptr;
-  size_t transient = 0;
-  auto tmalloc = [&](void** p, size_t bytes) -> int {
-    hipError_t er = hipMalloc(p, bytes);
-    if (er != hipSuccess) return e->fail(VC_ERR_HIP, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(er));
-    transient += bytes;
-    return VC_OK;
-  };
-  auto free_transients = [&]() {
-    for (int m = 0; m < 2; ++m) {
-      if (tab[m]) (void)hipFree(tab[m]);
-      if (ovf_val[m]) (void)hipFree(ovf_val[m]);
-      if (ovf_gene[m]) (void)hipFree(ovf_gene[m]);
-      tab[m] = nullptr; ovf_val[m] = nullptr; ovf_gene[m] = nullptr;
-    }
-    if (ovf_n) (void)hipFree(ovf_n);
-    if (bad) (void)hipFree(bad);
-    ovf_n = nullptr; bad = nullptr;
-  };
+  return VC_OK;
+}
+
+// HBM layout of the counts: [gene block][cell][gbw], zero padded in genes; the per-gene count histograms are built on
+// the device in the same pass (dense bins + overflow list), so that no dense matrix crosses back to the host
+static int fin_pack_counts(vc_engine* e, FinalizeState& s) {
+  VcDims& d = e->d;
+  VcBufs& b = e->b;
+  hipStream_t st = s.st;
+  unsigned** tab = s.scratch.tab;
+  float** ovf_val = s.scratch.ovf_val;
+  int** ovf_gene = s.scratch.ovf_gene;
+  unsigned*& ovf_n = s.scratch.ovf_n;
+  int*& bad = s.scratch.bad;
+  s.want_hist = d.noise != VC_NOISE_LOGNORMAL;
+  s.dev_hist = s.want_hist && !e->host_hist;
   // cells ordered by batch (one-hot batches that are not contiguous): the blocked counts, the cell table and the per-cell partial
   // rows live in that order; every per-cell kernel maps its cell through cell_pos (vc_common.h: vc_pos)
-  const int* dev_ord = nullptr;
   b.cell_pos = nullptr;
-  if (d.onehot && !bat_sorted) {
-    TRY(upload(e, bat_pos, &b.cell_pos));
-    TRY(upload(e, bat_ord, &dev_ord));
+  if (d.onehot && !s.bat_sorted) {
+    TRY(upload(e, s.bat_pos, &b.cell_pos));
+    TRY(upload(e, s.bat_ord, &s.dev_ord));
   }
-  TRY(tmalloc((void**)&ovf_n, 2 * sizeof(unsigned)));
-  TRY(tmalloc((void**)&bad, 4 * sizeof(int)));
+  TRY(s.scratch.alloc(e, &ovf_n, 2));
+  TRY(s.scratch.alloc(e, &bad, 4));
   HIPCHK(e, hipMemsetAsync(ovf_n, 0, 2 * sizeof(unsigned), st));
   HIPCHK(e, hipMemsetAsync(bad, 0, 4 * sizeof(int), st));
-  {
-    const size_t blocked = (size_t)d.nGB * d.Nc * d.gbw;
-    const float** dstp[2] = {&b.S, &b.U};
-    for (int m = 0; m < 2; ++m) {
-      *dstp[m] = nullptr;
-      auto& c = e->src[m];
-      if (c.kind == 0) continue;
-      for (void* p : c.owned) if (p) transient += 0;   // owned uploads are released below
-      float* packed = nullptr;
-      TRY(e->dalloc(&packed, blocked));
-      if (dev_hist) {
-        int rc = tmalloc((void**)&tab[m], (size_t)d.Ng * VC_HIST_CAP * sizeof(unsigned));
-        if (rc == VC_OK) rc = tmalloc((void**)&ovf_val[m], (size_t)OVF_CAP * sizeof(float));
-        if (rc == VC_OK) rc = tmalloc((void**)&ovf_gene[m], (size_t)OVF_CAP * sizeof(int));
-        if (rc != VC_OK) { free_transients(); return rc; }
-        HIPCHK(e, hipMemsetAsync(tab[m], 0, (size_t)d.Ng * VC_HIST_CAP * sizeof(unsigned), st));
-      }
-      const int ln = d.noise == VC_NOISE_LOGNORMAL;
-      if (c.kind == 1) {
-        vc_launch_pack_counts(c.dense, packed, e->dgs, e->dcs, d.Ng, d.Nc, d.nGB, d.gbw, ln, tab[m], ovf_val[m], ovf_gene[m],
-                              ovf_n + m, OVF_CAP, bad, dev_ord, st);
-      } else {
-        HIPCHK(e, hipMemsetAsync(packed, 0, blocked * sizeof(float), st));
-        vc_launch_scatter_csr(c.indptr, c.indices, c.data, packed, d.Ng, d.Nc, d.gbw, ln, tab[m], ovf_val[m], ovf_gene[m],
-                              ovf_n + m, OVF_CAP, bad, b.cell_pos, st);
-      }
-      HIPCHK(e, hipStreamSynchronize(st));
-      HIPCHK(e, hipGetLastError());
-      if (c.owned[0]) transient += (c.kind == 1 ? (size_t)d.Ng * d.Nc * 4 : (size_t)(d.Nc + 1) * 8 + (size_t)c.nnz * 8);
-      *dstp[m] = packed;
+  const size_t blocked = (size_t)d.nGB * d.Nc * d.gbw;
+  const float** dstp[2] = {&b.S, &b.U};
+  for (int m = 0; m < 2; ++m) {
+    *dstp[m] = nullptr;
+    auto& c = e->src[m];
+    if (c.kind == 0) continue;
+    float* packed = nullptr;
+    TRY(e->dalloc(&packed, blocked));
+    if (s.dev_hist) {
+      TRY(s.scratch.alloc(e, &tab[m], (size_t)d.Ng * VC_HIST_CAP));
+      TRY(s.scratch.alloc(e, &ovf_val[m], OVF_CAP));
+      TRY(s.scratch.alloc(e, &ovf_gene[m], OVF_CAP));
+      HIPCHK(e, hipMemsetAsync(tab[m], 0, (size_t)d.Ng * VC_HIST_CAP * sizeof(unsigned), st));
     }
-  }
-  {
-    int hbad[4] = {0, 0, 0, 0};
-    HIPCHK(e, hipMemcpy(hbad, bad, sizeof hbad, hipMemcpyDeviceToHost));
-    if (hbad[1]) { free_transients(); return e->fail(VC_ERR_ARG, "vc_set_counts_csr: gene index outside [0, Ng)"); }
-    if (hbad[0]) { free_transients(); return e->fail(VC_ERR_ARG, "count matrices must be finite and >= 0 (NaN / Inf / negative value found)"); }
-    // Count storage: when every count of this rank's matrices is an integer <= 65535 (checked by the pass above) the
-    // blocked layout is narrowed to uint16 -- half the bytes K_main streams per step; exact.  tuning.count_storage = 1 keeps
-    // the reference's float32 (A/B measurements, tests); Lognormal noise stores log(k + 1) and stays float32.
-    const bool want16 = e->tun.count_storage != 1 && d.noise != VC_NOISE_LOGNORMAL && !hbad[2] && !d.generic;
-    if (want16) {
-      const void* k16 = nullptr;
-      const char* nm = nullptr;
-      hipFuncAttributes fa;
-      vc_main_launch_fn f16 = vc_find_main_kernel(d.H, knb, d.kind, d.noise, d.gpl, 1, &nm, &k16);
-      vc_main_launch_fn p16 = d.kind == VC_KIND_VU ? vc_find_main_kernel(d.H, knb, VC_KIND_PHASE, d.noise, d.gpl, 1, nullptr, nullptr) : nullptr;
-      if (f16 && k16 && (d.kind != VC_KIND_VU || p16) && hipFuncGetAttributes(&fa, k16) == hipSuccess && fa.localSizeBytes <= max_scratch) {
-        const size_t blocked = (size_t)d.nGB * d.Nc * d.gbw;
-        const float** dstp[2] = {&b.S, &b.U};
-        for (int m = 0; m < 2; ++m) {
-          if (!*dstp[m]) continue;
-          unsigned short* p16buf = nullptr;
-          int rc = e->dalloc(&p16buf, blocked);
-          if (rc != VC_OK) { free_transients(); return rc; }
-          vc_launch_counts_to_u16(*dstp[m], p16buf, (long long)blocked, st);
-          HIPCHK(e, hipStreamSynchronize(st));
-          transient += blocked * sizeof(float);      // the float32 layout lives until its uint16 copy exists
-          e->dfree(*dstp[m]);
-          *dstp[m] = reinterpret_cast<const float*>(p16buf);
-        }
-        d.c16 = 1;
-        e->main_fn = f16;
-        main_kernel = k16;
-        if (p16) e->phase_fn = p16;
-      }
+    const int ln = d.noise == VC_NOISE_LOGNORMAL;
+    if (c.kind == 1) {
+      vc_launch_pack_counts(c.dense, packed, e->dgs, e->dcs, d.Ng, d.Nc, d.nGB, d.gbw, ln, tab[m], ovf_val[m], ovf_gene[m],
+                            ovf_n + m, OVF_CAP, bad, s.dev_ord, st);
+    } else {
+      HIPCHK(e, hipMemsetAsync(packed, 0, blocked * sizeof(float), st));
+      vc_launch_scatter_csr(c.indptr, c.indices, c.data, packed, d.Ng, d.Nc, d.gbw, ln, tab[m], ovf_val[m], ovf_gene[m],
+                            ovf_n + m, OVF_CAP, bad, b.cell_pos, st);
     }
+    HIPCHK(e, hipStreamSynchronize(st));
+    HIPCHK(e, hipGetLastError());
+    if (c.owned[0]) s.transient += (c.kind == 1 ? (size_t)d.Ng * d.Nc * 4 : (size_t)(d.Nc + 1) * 8 + (size_t)c.nnz * 8);
+    *dstp[m] = packed;
   }
+  int hbad[4] = {0, 0, 0, 0};
+  HIPCHK(e, hipMemcpy(hbad, bad, sizeof hbad, hipMemcpyDeviceToHost));
+  if (hbad[1]) return e->fail(VC_ERR_ARG, "vc_set_counts_csr: gene index outside [0, Ng)");
+  if (hbad[0]) return e->fail(VC_ERR_ARG, "count matrices must be finite and >= 0 (NaN / Inf / negative value found)");
+  // Count storage: when every count of this rank's matrices is an integer <= 65535 (checked by the pass above) the
+  // blocked layout is narrowed to uint16 -- half the bytes K_main streams per step; exact.  tuning.count_storage = 1 keeps
+  // the reference's float32 (A/B measurements, tests); Lognormal noise stores log(k + 1) and stays float32.
+  if (e->tun.count_storage == 1 || d.noise == VC_NOISE_LOGNORMAL || hbad[2] || d.generic) return VC_OK;
+  const void* k16 = nullptr;
+  vc_main_launch_fn f16 = find_main_noscratch(d, d.gpl, 1, &k16);
+  vc_main_launch_fn p16 = d.kind == VC_KIND_VU ? vc_find_main_kernel(d.H, d.nbk, VC_KIND_PHASE, d.noise, d.gpl, 1, nullptr, nullptr) : nullptr;
+  if (!f16 || (d.kind == VC_KIND_VU && !p16)) return VC_OK;
+  for (int m = 0; m < 2; ++m) {
+    if (!*dstp[m]) continue;
+    unsigned short* p16buf = nullptr;
+    TRY(e->dalloc(&p16buf, blocked));
+    vc_launch_counts_to_u16(*dstp[m], p16buf, (long long)blocked, st);
+    HIPCHK(e, hipStreamSynchronize(st));
+    s.transient += blocked * sizeof(float);      // the float32 layout lives until its uint16 copy exists
+    e->dfree(*dstp[m]);
+    *dstp[m] = reinterpret_cast<const float*>(p16buf);
+  }
+  d.c16 = 1;
+  e->main_fn = f16;
+  s.main_kernel = k16;
+  if (p16) e->phase_fn = p16;
+  return VC_OK;
+}
+
+// Tiling of the likelihood kernel: one balanced round.  The grid is sized to the workgroups the chip holds at once for
+// this kernel (occupancy x 256 CUs); each wave gets an equal share of the cells of its gene block,
+// so no partially filled last round is left over (a 2.04-round grid costs 3 rounds).  Also decides K_main's own nu_omega
+// partials and the gradient-only twin, and uploads the workgroup table.
+static int fin_tiling(vc_engine* e, FinalizeState& s) {
+  VcDims& d = e->d;
+  VcBufs& b = e->b;
+  const void*& main_kernel = s.main_kernel;
   std::vector<int> tile_host, bat_chunk_host;      // the workgroup table / the batches' chunk ranges (one-hot batches: built with the tiling)
-  // tiling: one balanced round.  The grid is sized to the workgroups the chip holds at once for
-  // this kernel (occupancy x 256 CUs); each wave gets an equal share of the cells of its gene block,
-  // so no partially filled last round is left over (a 2.04-round grid costs 3 rounds).
-  {
-    int n_cu = 256;
-    hipDeviceProp_t prop;
-    int dev = 0;
-    HIPCHK(e, hipGetDevice(&dev));
-    HIPCHK(e, hipGetDeviceProperties(&prop, dev));
-    if (prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-    const int wg_waves = d.generic ? 1 : VC_WAVES;
-    const unsigned gen_dyn = d.generic ? (unsigned)(2 * d.K * 64 * 2 * sizeof(float)) : 0u;      // nu~ and gradient rows of one wave
-    auto occupancy = [&](unsigned dyn_bytes, int* out) -> int {
-      int bpc = 0;
-      dyn_bytes += gen_dyn;
-      if (dyn_bytes > 0) {
-        // the per-gene state of the run-time-sized kernels / the staged W rows must fit the LDS a workgroup of THIS device may ask
-        // for (gfx950: 160 KB; a part with 64 KB refuses here with the dimension named instead of failing at launch: ADVICE r4)
-        const size_t lds_cap = std::max<size_t>(prop.sharedMemPerBlockOptin, prop.maxSharedMemoryPerMultiProcessor);
-        hipError_t er = lds_cap > 0 && dyn_bytes > lds_cap ? hipErrorInvalidValue
-                                                            : hipFuncSetAttribute(main_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes);
-        if (er != hipSuccess) {
-          (void)hipGetLastError();
-          return e->fail(VC_ERR_UNSUPPORTED, "the likelihood kernel needs %u bytes of LDS per workgroup (2 n_harmonics + 1 + Nb = %d coefficient rows per gene"
-                                             "%s), this device grants %zu", dyn_bytes, d.K, d.generic ? " on the run-time-sized kernel set" : "", lds_cap);
-        }
-      }
-      HIPCHK(e, hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, main_kernel, 64 * wg_waves, dyn_bytes));
-      if (d.generic && bpc > 8) bpc = 8;      // (one wave each: two per SIMD hide the LDS latency, more only shorten the runs of cells)
-      if (e->tun.blocks_per_cu > 0) bpc = e->tun.blocks_per_cu;
-      *out = bpc;
-      return VC_OK;
-    };
-    // Unequal shares per dispatch pass.  The workgroups of pass p (the p-th one on every CU) are older than those of pass
-    // p + 1 and the SIMD arbiter issues the oldest ready wave first: with equal shares the first pass ends its cells at
-    // ~60 % of the kernel and the last pass then runs alone, one wave per SIMD (profiles/tools/wave_timeline.py).  Measured
-    // (profiles/r02_pass_shares.md): shares falling by 1/2 per pass (2 passes 0.67 : 0.33, 3 passes 0.57 : 0.29 : 0.14) cut the
-    // kernel by 5-9 %; that is the default for a full multi-pass grid.  tuning.pass_shares overrides (n_pass_shares = 1: the
-    // balanced tiling).  The tiling (vc_host_logic.h, also what the kernel evaluates per wave) stays a pure function of
-    // (Nc, Ng, occupancy, CUs): results are reproducible.
-    auto tile = [&](int blocks_per_cu) {
-      if (blocks_per_cu < 1) blocks_per_cu = 1;
-      tile_host.clear(); bat_chunk_host.clear();
-      double share[4] = {1.0, 0.5, 0.25, 0.125};
-      if (d.kind == VC_KIND_VFULL && blocks_per_cu == 2) {
-        // round 3: with two cells of the S+U kernel's counts in flight (hand-placed waits) the older wave of a SIMD stalls less
-        // and leaves the younger one fewer issue slots: 0.67 : 0.33 ends the passes at 104 / 120 us, 0.75 : 0.25 together
-        // (profiles/r03_kmain.md: 119.4 vs 121.4 us)
-        share[1] = 1.0 / 3.0; share[2] = 1.0 / 9.0; share[3] = 1.0 / 27.0;
-      } else if (d.kind != VC_KIND_VFULL && blocks_per_cu == 3) {
-        // the three-pass one-matrix kernels: 0.62 : 0.26 : 0.12 instead of 0.57 : 0.29 : 0.14 (the third pass ended 12 us after
-        // the first): phase 58.3 -> 56.2-56.9 us, U only 70.6 -> 70.0-70.1 us (profiles/r03_kmain.md section 3)
-        share[1] = 0.42; share[2] = 0.19; share[3] = 0.09;
-      }
-      bool want = true;
-      if (e->tun.n_pass_shares == 1) want = false;                  // equal shares: the balanced tiling
-      else if (e->tun.n_pass_shares >= 2) {
-        const int n = e->tun.n_pass_shares;
-        for (int p = 0; p < n; ++p) share[p] = (double)e->tun.pass_shares[p];
-        for (int p = n; p < 4; ++p) share[p] = share[p - 1] * (share[n - 1] / share[n - 2]);
-      }
-      // below 12 cells per wave the passes' fixed prologue / epilogue dominate (measured at the 6 250-cell shard)
-      const VcTiling t = vc_tile_cells(d.Nc, d.nGB, n_cu, blocks_per_cu, wg_waves, e->tun.cells_per_wave,
-                                       (want && !d.generic) ? share : nullptr, e->tun.pass_min_cw > 0 ? e->tun.pass_min_cw : 12);
-      d.cw = t.cw;
-      d.n_chunks = t.n_chunks;
-      d.pass_wgs = n_cu;
-      for (int p = 0; p < 4; ++p) d.pass_cw[p] = t.pass_cw[p];
-      if (d.onehot) {
-        // every workgroup inside one batch: the chunks of a gene block are dealt out to the batches in proportion to their cells
-        // (vc_host_logic.h: vc_tile_batches); a non-empty batch needs at least one chunk
-        int nonempty = 0;
-        for (int v : bat_len) nonempty += v > 0;
-        if (d.n_chunks < nonempty) d.n_chunks = nonempty;
-        const int cwm = vc_tile_batches(d.Nc, d.nGB, d.n_chunks, d.pass_wgs, d.pass_cw, wg_waves, bat_len, tile_host, bat_chunk_host);
-        if (cwm > d.cw) d.cw = cwm;
-      }
-      d.n_main_wg = d.nGB * d.n_chunks;
-    };
-    int bpc0 = 0;
-    TRY(occupancy(0, &bpc0));
-    tile(bpc0);
-    // K_main's own partials of d loglik / d nu_omega (vc_common.h: VC_PW_INLINE; one rank, <= VC_PWQ coefficients): the W rows of a
-    // wave's cells are staged in DYNAMIC shared memory, which may cost the kernel a resident workgroup per CU -- the tiling
-    // follows the occupancy the launch will really have (at most one adjustment; if even that does not fit: off)
-    d.pw_inline = 0;
-    d.pw_slots = 0;
-    const bool pw_kind = VC_PW_INLINE && (d.kind == VC_KIND_VU || d.kind == VC_KIND_VFULL) && d.NW >= 1 && d.NW <= VC_PWQ &&
-                         e->cfg.world_size == 1 && !d.generic;
-    d.pw_lane = 0;
-    const bool lane_conds = e->D_all_ones || (d.onehot && !e->bat_cond.empty());     // one condition per workgroup of K_main
-    if (pw_kind && e->tun.pw_inline != 1 && d.kind == VC_KIND_VU && lane_conds && d.Hw <= d.H && !e->tun.no_pw_lane) {
-      // Round 6: ONE condition with D == 1 (every one-sample fit): the W row of a cell is (1, sin k phi_c, cos k phi_c) -- what its
-      // record already holds as wave-uniform SGPR pairs.  The U-only kernel's PWL instantiation (count storage | 4) accumulates
-      // A3 x W per LANE (1 + 2 Hw plain VALU per cell) instead of reducing A3 over the wave first (a 64-lane DPP tree + staging
-      // per cell): no W rows in the LDS, no per-cell rows stored (nothing reads them once K_main delivers the partials itself).
-      const void* kl = nullptr;
-      const char* nm = nullptr;
-      hipFuncAttributes fa;
-      vc_main_launch_fn fl = vc_find_main_kernel(d.H, knb, d.kind, d.noise, d.gpl, d.c16 | 4, &nm, &kl);
-      if (fl && kl && hipFuncGetAttributes(&fa, kl) == hipSuccess && fa.localSizeBytes == 0) {
-        e->main_fn_rows = e->main_fn;       // the instantiation that stores per-cell rows: what the sharded phases launch (vc_svi_run_sharded)
-        e->main_fn = fl;
-        main_kernel = kl;
-        d.pw_inline = d.NW <= 4 ? 4 : 8;
-        d.pw_slots = 0;
-        d.pw_lane = 1;
-        // (without the staging registers of the wave-level reduction this instantiation needs 120 VGPRs instead of 160: four
-        // workgroups per CU instead of three -- the tiling follows the occupancy of the kernel that will run)
-        int bl = 0;
-        TRY(occupancy(0, &bl));
-        if (bl != bpc0) tile(bl);
+  const int wg_waves = d.generic ? 1 : VC_WAVES;
+  const unsigned gen_dyn = d.generic ? (unsigned)(2 * d.K * 64 * 2 * sizeof(float)) : 0u;      // nu~ and gradient rows of one wave
+  auto occupancy = [&](unsigned dyn_bytes, int* out) -> int {
+    int bpc = 0;
+    dyn_bytes += gen_dyn;
+    if (dyn_bytes > 0) {
+      // the per-gene state of the run-time-sized kernels / the staged W rows must fit the LDS a workgroup of THIS device may ask
+      // for (gfx950: 160 KB; a part with 64 KB refuses here with the dimension named instead of failing at launch: ADVICE r4)
+      hipError_t er = s.lds_cap > 0 && dyn_bytes > s.lds_cap ? hipErrorInvalidValue
+                                                              : hipFuncSetAttribute(main_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes);
+      if (er != hipSuccess) {
+        (void)hipGetLastError();
+        return e->fail(VC_ERR_UNSUPPORTED, "the likelihood kernel needs %u bytes of LDS per workgroup (2 n_harmonics + 1 + Nb = %d coefficient rows per gene"
+                                           "%s), this device grants %zu", dyn_bytes, d.K, d.generic ? " on the run-time-sized kernel set" : "", s.lds_cap);
       }
     }
-    if (d.pw_lane) {
-    } else
-    if (pw_kind && e->tun.pw_inline != 1) {
-      const int row = d.NW <= 4 ? 4 : 8;
-      int bpc = bpc0;
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        const int cwmax = std::max(d.cw, std::max(std::max(d.pass_cw[0], d.pass_cw[1]), std::max(d.pass_cw[2], d.pass_cw[3])));
-        VcDims probe = d;
-        probe.pw_inline = row;
-        probe.pw_slots = (cwmax * (row / 4) + 15) / 16 * 16;
-        const unsigned dyn = vc_main_dyn_lds(probe);
-        int got = 0;
-        if (dyn > 96u * 1024u || occupancy(dyn, &got) != VC_OK || got < 1) break;
-        if (got == bpc) { d.pw_inline = row; d.pw_slots = probe.pw_slots; break; }
-        // The W rows would cost a resident workgroup per CU (the 4-genes-per-lane S+U kernel: its reduction tiles already take
-        // 52 KB of LDS, three workgroups just fit).  Measured at 2 000 genes (profiles/r04_small_shard.md): K_main 58.9 -> 70.8 us
-        // at 25 000 cells, 33.6 -> 40.1 at 12 500, 23.0 -> 24.6 at 6 250 -- more than the launch it saves, except where a wave
-        // has so few cells that the kernel is prologue and epilogue anyway: accepted only there.
-        if (d.cw > 12 && e->tun.pw_inline != 2) break;      // (tuning.pw_inline = 2: accept the loss anyway -- tests, A/B)
-        bpc = got;                      // tile for the occupancy that is left and look again
-        tile(bpc);
-      }
-      if (!d.pw_inline) tile(bpc0);     // off: the tiling of the plain kernel
+    HIPCHK(e, hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, main_kernel, 64 * wg_waves, dyn_bytes));
+    if (d.generic && bpc > 8) bpc = 8;      // (one wave each: two per SIMD hide the LDS latency, more only shorten the runs of cells)
+    if (e->tun.blocks_per_cu > 0) bpc = e->tun.blocks_per_cu;
+    *out = bpc;
+    return VC_OK;
+  };
+  // Unequal shares per dispatch pass.  The workgroups of pass p (the p-th one on every CU) are older than those of pass
+  // p + 1 and the SIMD arbiter issues the oldest ready wave first: with equal shares the first pass ends its cells at
+  // ~60 % of the kernel and the last pass then runs alone, one wave per SIMD (profiles/tools/wave_timeline.py).  Measured
+  // (profiles/r02_pass_shares.md): shares falling by 1/2 per pass (2 passes 0.67 : 0.33, 3 passes 0.57 : 0.29 : 0.14) cut the
+  // kernel by 5-9 %; that is the default for a full multi-pass grid.  tuning.pass_shares overrides (n_pass_shares = 1: the
+  // balanced tiling).  The tiling (vc_host_logic.h, also what the kernel evaluates per wave) stays a pure function of
+  // (Nc, Ng, occupancy, CUs): results are reproducible.
+  auto tile = [&](int blocks_per_cu) {
+    if (blocks_per_cu < 1) blocks_per_cu = 1;
+    tile_host.clear(); bat_chunk_host.clear();
+    double share[4] = {1.0, 0.5, 0.25, 0.125};
+    if (d.kind == VC_KIND_VFULL && blocks_per_cu == 2) {
+      // round 3: with two cells of the S+U kernel's counts in flight (hand-placed waits) the older wave of a SIMD stalls less
+      // and leaves the younger one fewer issue slots: 0.67 : 0.33 ends the passes at 104 / 120 us, 0.75 : 0.25 together
+      // (profiles/r03_kmain.md: 119.4 vs 121.4 us)
+      share[1] = 1.0 / 3.0; share[2] = 1.0 / 9.0; share[3] = 1.0 / 27.0;
+    } else if (d.kind != VC_KIND_VFULL && blocks_per_cu == 3) {
+      // the three-pass one-matrix kernels: 0.62 : 0.26 : 0.12 instead of 0.57 : 0.29 : 0.14 (the third pass ended 12 us after
+      // the first): phase 58.3 -> 56.2-56.9 us, U only 70.6 -> 70.0-70.1 us (profiles/r03_kmain.md section 3)
+      share[1] = 0.42; share[2] = 0.19; share[3] = 0.09;
     }
+    bool want = true;
+    if (e->tun.n_pass_shares == 1) want = false;                  // equal shares: the balanced tiling
+    else if (e->tun.n_pass_shares >= 2) {
+      const int n = e->tun.n_pass_shares;
+      for (int p = 0; p < n; ++p) share[p] = (double)e->tun.pass_shares[p];
+      for (int p = n; p < 4; ++p) share[p] = share[p - 1] * (share[n - 1] / share[n - 2]);
+    }
+    // below 12 cells per wave the passes' fixed prologue / epilogue dominate (measured at the 6 250-cell shard)
+    const VcTiling t = vc_tile_cells(d.Nc, d.nGB, s.n_cu, blocks_per_cu, wg_waves, e->tun.cells_per_wave,
+                                     (want && !d.generic) ? share : nullptr, e->tun.pass_min_cw > 0 ? e->tun.pass_min_cw : 12);
+    d.cw = t.cw;
+    d.n_chunks = t.n_chunks;
+    d.pass_wgs = s.n_cu;
+    for (int p = 0; p < 4; ++p) d.pass_cw[p] = t.pass_cw[p];
+    if (d.onehot) {
+      // every workgroup inside one batch: the chunks of a gene block are dealt out to the batches in proportion to their cells
+      // (vc_host_logic.h: vc_tile_batches); a non-empty batch needs at least one chunk
+      int nonempty = 0;
+      for (int v : s.bat_len) nonempty += v > 0;
+      if (d.n_chunks < nonempty) d.n_chunks = nonempty;
+      const int cwm = vc_tile_batches(d.Nc, d.nGB, d.n_chunks, d.pass_wgs, d.pass_cw, wg_waves, s.bat_len, tile_host, bat_chunk_host);
+      if (cwm > d.cw) d.cw = cwm;
+    }
+    d.n_main_wg = d.nGB * d.n_chunks;
+  };
+  int bpc0 = 0;
+  TRY(occupancy(0, &bpc0));
+  tile(bpc0);
+  // K_main's own partials of d loglik / d nu_omega (vc_common.h: VC_PW_INLINE; one rank, <= VC_PWQ coefficients): the W rows of a
+  // wave's cells are staged in DYNAMIC shared memory, which may cost the kernel a resident workgroup per CU -- the tiling
+  // follows the occupancy the launch will really have (at most one adjustment; if even that does not fit: off)
+  d.pw_inline = 0;
+  d.pw_slots = 0;
+  const bool pw_kind = VC_PW_INLINE && (d.kind == VC_KIND_VU || d.kind == VC_KIND_VFULL) && d.NW >= 1 && d.NW <= VC_PWQ &&
+                       e->cfg.world_size == 1 && !d.generic;
+  d.pw_lane = 0;
+  const bool lane_conds = e->D_all_ones || (d.onehot && !e->bat_cond.empty());     // one condition per workgroup of K_main
+  if (pw_kind && e->tun.pw_inline != 1 && d.kind == VC_KIND_VU && lane_conds && d.Hw <= d.H && !e->tun.no_pw_lane) {
+    // Round 6: ONE condition with D == 1 (every one-sample fit): the W row of a cell is (1, sin k phi_c, cos k phi_c) -- what its
+    // record already holds as wave-uniform SGPR pairs.  The U-only kernel's PWL instantiation (count storage | 4) accumulates
+    // A3 x W per LANE (1 + 2 Hw plain VALU per cell) instead of reducing A3 over the wave first (a 64-lane DPP tree + staging
+    // per cell): no W rows in the LDS, no per-cell rows stored (nothing reads them once K_main delivers the partials itself).
+    const void* kl = nullptr;
+    vc_main_launch_fn fl = find_main_noscratch(d, d.gpl, d.c16 | 4, &kl);
+    if (fl) {
+      e->main_fn_rows = e->main_fn;       // the instantiation that stores per-cell rows: what the sharded phases launch (vc_svi_run_sharded)
+      e->main_fn = fl;
+      main_kernel = kl;
+      d.pw_inline = d.NW <= 4 ? 4 : 8;
+      d.pw_slots = 0;
+      d.pw_lane = 1;
+      // (without the staging registers of the wave-level reduction this instantiation needs 120 VGPRs instead of 160: four
+      // workgroups per CU instead of three -- the tiling follows the occupancy of the kernel that will run)
+      int bl = 0;
+      TRY(occupancy(0, &bl));
+      if (bl != bpc0) tile(bl);
+    }
+  }
+  if (!d.pw_lane && pw_kind && e->tun.pw_inline != 1) {
+    const int row = d.NW <= 4 ? 4 : 8;
+    int bpc = bpc0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      const int cwmax = std::max(d.cw, std::max(std::max(d.pass_cw[0], d.pass_cw[1]), std::max(d.pass_cw[2], d.pass_cw[3])));
+      VcDims probe = d;
+      probe.pw_inline = row;
+      probe.pw_slots = (cwmax * (row / 4) + 15) / 16 * 16;
+      const unsigned dyn = vc_main_dyn_lds(probe);
+      int got = 0;
+      if (dyn > 96u * 1024u || occupancy(dyn, &got) != VC_OK || got < 1) break;
+      if (got == bpc) { d.pw_inline = row; d.pw_slots = probe.pw_slots; break; }
+      // The W rows would cost a resident workgroup per CU (the 4-genes-per-lane S+U kernel: its reduction tiles already take
+      // 52 KB of LDS, three workgroups just fit).  Measured at 2 000 genes (profiles/r04_small_shard.md): K_main 58.9 -> 70.8 us
+      // at 25 000 cells, 33.6 -> 40.1 at 12 500, 23.0 -> 24.6 at 6 250 -- more than the launch it saves, except where a wave
+      // has so few cells that the kernel is prologue and epilogue anyway: accepted only there.
+      if (d.cw > 12 && e->tun.pw_inline != 2) break;      // (tuning.pw_inline = 2: accept the loss anyway -- tests, A/B)
+      bpc = got;                      // tile for the occupancy that is left and look again
+      tile(bpc);
+    }
+    if (!d.pw_inline) tile(bpc0);     // off: the tiling of the plain kernel
   }
   if (!d.generic && d.noise == VC_NOISE_NB) {
     // the gradient-only twin of the selected kernel (same tiling, same dynamic LDS); used only after vc_set_loss_every(k > 1)
     const void* knl = nullptr;
-    e->main_fn_nl = vc_find_main_kernel(d.H, knb, d.kind, d.noise, d.gpl, d.c16 | 2 | (d.pw_lane ? 4 : 0), &e->main_name_nl, &knl);
-    hipFuncAttributes fa;
-    if (e->main_fn_nl && knl && (hipFuncGetAttributes(&fa, knl) != hipSuccess || fa.localSizeBytes > 0)) e->main_fn_nl = nullptr;
+    e->main_fn_nl = find_main_noscratch(d, d.gpl, d.c16 | 2 | (d.pw_lane ? 4 : 0), &knl);
     const unsigned dyn = vc_main_dyn_lds(d);
     if (e->main_fn_nl && dyn > 0 && hipFuncSetAttribute(knl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
       (void)hipGetLastError();
       e->main_fn_nl = nullptr;          // (no gradient-only twin then: vc_set_loss_every says so)
     }
   }
-  {
-    // the tiling as a table: {first cell of wave 0, cells per wave} of every workgroup of the likelihood kernel, evaluated
-    // HERE by the function the kernel used to run itself (vc_host_logic.h; 64-bit divisions = ~700 scalar instructions in
-    // front of every wave's first load)
-    // {first cell, cells per wave, batch, end of the workgroup's cells}; one-hot batches: the batch-aligned table built with the tiling
-    if (!d.onehot) {
-      tile_host.assign(4 * (size_t)d.n_main_wg, 0);
-      for (int w = 0; w < d.n_main_wg; ++w) {
-        int cw = 0;
-        const long long first = vc_wave_first_cell(w / d.nGB, w % d.nGB, 0, d.nGB, d.pass_wgs, d.pass_cw, d.generic ? 1 : VC_WAVES, &cw);
-        tile_host[4 * (size_t)w] = (int)std::min<long long>(first, (long long)d.Nc);
-        tile_host[4 * (size_t)w + 1] = cw;
-        tile_host[4 * (size_t)w + 3] = d.Nc;
-      }
-      b.bat_chunk = nullptr;
-    } else {
-      if (tile_host.size() != 4 * (size_t)d.n_main_wg) return e->fail(VC_ERR_STATE, "internal: batch-aligned tile table of the wrong size");
-      TRY(upload(e, bat_chunk_host, &b.bat_chunk));
-      if (d.pw_lane && !e->bat_cond.empty())       // {.., batch | condition << 16, ..}: the PWL kernel places its partials in its condition's columns
-        for (int w = 0; w < d.n_main_wg; ++w) {
-          const int q = tile_host[4 * (size_t)w + 2];
-          tile_host[4 * (size_t)w + 2] = q | (e->bat_cond[(size_t)q] << 16);
-        }
+  // the tiling as a table: {first cell of wave 0, cells per wave} of every workgroup of the likelihood kernel, evaluated
+  // HERE by the function the kernel used to run itself (vc_host_logic.h; 64-bit divisions = ~700 scalar instructions in
+  // front of every wave's first load)
+  // {first cell, cells per wave, batch, end of the workgroup's cells}; one-hot batches: the batch-aligned table built with the tiling
+  if (!d.onehot) {
+    tile_host.assign(4 * (size_t)d.n_main_wg, 0);
+    for (int w = 0; w < d.n_main_wg; ++w) {
+      int cw = 0;
+      const long long first = vc_wave_first_cell(w / d.nGB, w % d.nGB, 0, d.nGB, d.pass_wgs, d.pass_cw, d.generic ? 1 : VC_WAVES, &cw);
+      tile_host[4 * (size_t)w] = (int)std::min<long long>(first, (long long)d.Nc);
+      tile_host[4 * (size_t)w + 1] = cw;
+      tile_host[4 * (size_t)w + 3] = d.Nc;
     }
-    TRY(upload(e, tile_host, &b.wg_tile));
+    b.bat_chunk = nullptr;
+  } else {
+    if (tile_host.size() != 4 * (size_t)d.n_main_wg) return e->fail(VC_ERR_STATE, "internal: batch-aligned tile table of the wrong size");
+    TRY(upload(e, bat_chunk_host, &b.bat_chunk));
+    if (d.pw_lane && !e->bat_cond.empty())       // {.., batch | condition << 16, ..}: the PWL kernel places its partials in its condition's columns
+      for (int w = 0; w < d.n_main_wg; ++w) {
+        const int q = tile_host[4 * (size_t)w + 2];
+        tile_host[4 * (size_t)w + 2] = q | (e->bat_cond[(size_t)q] << 16);
+      }
   }
-  if (dev_ord) { e->dfree(dev_ord); dev_ord = nullptr; }
+  TRY(upload(e, tile_host, &b.wg_tile));
+  if (s.dev_ord) { e->dfree(s.dev_ord); s.dev_ord = nullptr; }      // (its last reader was the count pass)
+  return VC_OK;
+}
+
+// Block counts of the small kernels, the launch that follows K_main, priors, site values and the per-step workspaces
+static int fin_step_buffers(vc_engine* e) {
+  VcDims& d = e->d;
+  VcBufs& b = e->b;
+  const bool vel = d.model == VC_MODEL_VELOCITY;
+  const bool nb = d.noise == VC_NOISE_NB;
   d.nb_pre_gene = d.Ng_pad / 64;       // 64 genes per block, the sites of a gene spread over its 4 waves
   d.nb_pre_cell = (d.Nc + 255) / 256;
   d.nb_post_gene = d.Ng_pad / 64;
@@ -1114,6 +1142,7 @@ static int finalize_impl(vc_engine* e, void* hip_stream) {
   d.nmat_r = nb ? (d.kind == VC_KIND_VFULL ? 2 : 1) : 0;
   e->hist_each_step = nb && !cond(e, VC_SITE_SHAPE_INV);
   d.hist_par = e->hist_each_step ? 1 : 0;
+  e->tail_kind = choose_tail_kind(e);      // (its inputs are final here: the tiling's pw_inline, hist_each_step)
 
   // uploads
   TRY(upload(e, e->h_prior[VC_PRIOR_MU_NU], &b.mu_nu));
@@ -1144,7 +1173,7 @@ static int finalize_impl(vc_engine* e, void* hip_stream) {
   TRY(e->dalloc(&b.lat_phi, (size_t)d.Nc));
   TRY(e->dalloc(&b.lat_omega, (size_t)d.Nc));
   TRY(e->dalloc(&b.lat_domega, (size_t)d.Nc));
-  const int nq_max = std::max(d.nq, d.kind == VC_KIND_VU ? nq_of(VC_KIND_PHASE) : 0);
+  const int nq_max = std::max(d.nq, d.kind == VC_KIND_VU ? nq_of(d, VC_KIND_PHASE) : 0);
   TRY(e->dalloc(&b.GO, (size_t)d.n_chunks * nq_max * d.Ng_pad));
   TRY(e->dalloc(&b.CO, (size_t)d.nGB * 3 * d.Nc));
   HIPCHK(e, hipMemset(b.CO, 0, sizeof(float) * (size_t)d.nGB * 3 * d.Nc));   // (pw_lane: K_main stores no per-cell rows; their unfused readers see zeros)
@@ -1154,7 +1183,7 @@ static int finalize_impl(vc_engine* e, void* hip_stream) {
   HIPCHK(e, hipMemset(b.dbg, 0, VC_DBG_WORDS(d.n_main_wg) * 8));
 #endif
   TRY(e->dalloc(&b.LP, (size_t)(d.nb_pre_gene + d.nb_pre_cell + d.nb_post_gene)));
-  // (pw_inline -- the angular-speed gradient partials out of K_main -- was decided with the tiling above)
+  // (pw_inline -- the angular-speed gradient partials out of K_main -- was decided with the tiling)
   TRY(e->dalloc(&b.PWM, (size_t)d.n_main_wg * VC_PWQ));
   HIPCHK(e, hipMemset(b.PWM, 0, sizeof(float) * (size_t)d.n_main_wg * VC_PWQ));
   TRY(e->dalloc(&b.WT, (size_t)VC_PWQ * d.Nc));
@@ -1168,13 +1197,13 @@ static int finalize_impl(vc_engine* e, void* hip_stream) {
   // of it holds a CU on its own: with 256-cell blocks the cell blocks alone take most of the chip's 256 slots and the others
   // wait a round (50k x 2k: phase 17.5 -> 13.0 us outside K_main with 1024-cell blocks, V-joint 25 -> 22.5)
   // -- and with the dense histogram tables (S+U kernel) 512: its cell blocks carry the longest chain of that launch (nu_omega inside)
-  if (fused_tail_kind(e) == 2 && d.Nc > 16384) d.tail_tc = d.kind == VC_KIND_VFULL ? 512 : 1024;
+  if (e->tail_kind == 2 && d.Nc > 16384) d.tail_tc = d.kind == VC_KIND_VFULL ? 512 : 1024;
   if (e->tun.tail_cells) d.tail_tc = e->tun.tail_cells;
   if (e->tun.p2p_one_launch && e->cfg.world_size >= 1 && d.Nc <= 160000) d.tail_tc = 256;      // vc_tail_x_kernel: cell block = K_omega's block
   d.nb_tail_cell = (d.Nc + d.tail_tc - 1) / d.tail_tc;
   d.nlpf = d.nb_post_gene + d.nb_tail_cell + 1;
   d.lgamma_alpha = lgammaf(d.gamma_alpha);
-  d.spec = VC_SPEC_NONE;      // (chosen at the end: the histogram form below is part of the signature)
+  d.spec = VC_SPEC_NONE;      // (chosen at the end: the histogram form is part of the signature)
   {
     // exchange buffer of the sharded fused step (include/velocycle_hip.h): gradient region, PW rows, loss pairs
     const long long world = e->cfg.world_size, ncg = e->cfg.Nc_global > 0 ? e->cfg.Nc_global : d.Nc;
@@ -1208,153 +1237,171 @@ static int finalize_impl(vc_engine* e, void* hip_stream) {
   HIPCHK(e, hipMemset(b.step_size, 0, 2 * sizeof(float)));
   TRY(e->dalloc(&b.status, 4));       // [0] steps with a non-finite loss, [1] 1 + the first of them, [2] 1 + step of an exchange time-out
   HIPCHK(e, hipMemset(b.status, 0, 4 * sizeof(long long)));
+  return VC_OK;
+}
 
-  // histograms + step-invariant constants -----------------------------------------------------
-  double lg_S = 0.0, lg_U = 0.0;   // sum lgamma(k+1)
-  {
-    std::vector<int> ptr;
-    std::vector<float> val, cnt;
-    bool dense_ok = false;
-    std::vector<float> hc;
-    std::vector<int> hc_off, hc_rows;
-    if (want_hist) {
-      bool bad_host = false, fallback = false;
-      unsigned novf[2] = {0, 0};
-      if (dev_hist) {
-        HIPCHK(e, hipMemcpy(novf, ovf_n, sizeof novf, hipMemcpyDeviceToHost));
-        fallback = novf[0] > OVF_CAP || novf[1] > OVF_CAP;     // mostly non-integer data: the overflow list does not hold it
-      }
-      if (dev_hist && !fallback) {
-        std::vector<unsigned> htab((size_t)d.Ng * VC_HIST_CAP);
-        // dense tail-count tables (vc_host_logic.h: vc_build_dense_hist) when every non-zero count of the matrices is an integer
-        // below VC_HIST_CAP (no overflow entries): the histogram sums then cost a logarithm and a reciprocal per (gene, count
-        // level) and are evaluated per gene block.
-        // Default: the S+U kernel's models only -- 4 000+ task waves there (two matrices) against 32 blocks; measured at 50k x 2k
-        // (profiles/r04_two_launch.md) V-joint 21-24 -> 17.5-19 us outside K_main, phase (one matrix, nothing to hide the blocks
-        // of its few outlier genes behind) 13.4 -> 15.5: the phase model keeps the lists.  tuning.hist_dense = 2 / 1 forces either.
-        // Only where the one-launch tail runs (single rank with K_main's own nu_omega partials): through K_omega's / K_pre's
-        // 4-wave blocks the dense evaluation is slower than the lists (6 250-cell shard: sharded step 41.6 -> 44.2 us).
-        dense_ok = nb && novf[0] == 0 && novf[1] == 0 && d.Nc <= (1 << 24) &&
-                   (e->tun.hist_dense ? e->tun.hist_dense == 2 : (d.kind == VC_KIND_VFULL && fused_tail_kind(e) == 2));
-        for (int m = 0; m < (vel ? 2 : 1); ++m) {
-          HIPCHK(e, hipMemcpy(htab.data(), tab[m], htab.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-          if (dense_ok) vc_build_dense_hist(htab.data(), d.Ng, d.Ng_pad, hc, hc_off, hc_rows);
-          std::vector<float> ov(novf[m]);
-          std::vector<int> og(novf[m]);
-          if (novf[m]) {
-            HIPCHK(e, hipMemcpy(ov.data(), ovf_val[m], novf[m] * sizeof(float), hipMemcpyDeviceToHost));
-            HIPCHK(e, hipMemcpy(og.data(), ovf_gene[m], novf[m] * sizeof(int), hipMemcpyDeviceToHost));
-          }
-          std::vector<std::pair<int, float>> ovf(novf[m]);
-          for (unsigned i = 0; i < novf[m]; ++i) ovf[i] = {og[i], ov[i]};
-          const double lg = vc_compact_hist(htab.data(), d.Ng, ovf, ptr, val, cnt);
-          (m == 0 ? lg_S : lg_U) = lg;
+// Count histograms (from the device tables of the count pass, or from a host copy of the counts), their dense tables and the task
+// list of the histogram kernel; releases the set-up scratch and the count sources
+static int fin_histograms(vc_engine* e, FinalizeState& s) {
+  VcDims& d = e->d;
+  VcBufs& b = e->b;
+  const bool vel = d.model == VC_MODEL_VELOCITY;
+  const bool nb = d.noise == VC_NOISE_NB;
+  unsigned** tab = s.scratch.tab;
+  float** ovf_val = s.scratch.ovf_val;
+  int** ovf_gene = s.scratch.ovf_gene;
+  unsigned* ovf_n = s.scratch.ovf_n;
+  std::vector<int> ptr;
+  std::vector<float> val, cnt;
+  bool dense_ok = false;
+  std::vector<float> hc;
+  std::vector<int> hc_off, hc_rows;
+  if (s.want_hist) {
+    bool bad_host = false, fallback = false;
+    unsigned novf[2] = {0, 0};
+    if (s.dev_hist) {
+      HIPCHK(e, hipMemcpy(novf, ovf_n, sizeof novf, hipMemcpyDeviceToHost));
+      fallback = novf[0] > OVF_CAP || novf[1] > OVF_CAP;     // mostly non-integer data: the overflow list does not hold it
+    }
+    if (s.dev_hist && !fallback) {
+      std::vector<unsigned> htab((size_t)d.Ng * VC_HIST_CAP);
+      // dense tail-count tables (vc_host_logic.h: vc_build_dense_hist) when every non-zero count of the matrices is an integer
+      // below VC_HIST_CAP (no overflow entries): the histogram sums then cost a logarithm and a reciprocal per (gene, count
+      // level) and are evaluated per gene block.
+      // Default: the S+U kernel's models only -- 4 000+ task waves there (two matrices) against 32 blocks; measured at 50k x 2k
+      // (profiles/r04_two_launch.md) V-joint 21-24 -> 17.5-19 us outside K_main, phase (one matrix, nothing to hide the blocks
+      // of its few outlier genes behind) 13.4 -> 15.5: the phase model keeps the lists.  tuning.hist_dense = 2 / 1 forces either.
+      // Only where the one-launch tail runs (single rank with K_main's own nu_omega partials): through K_omega's / K_pre's
+      // 4-wave blocks the dense evaluation is slower than the lists (6 250-cell shard: sharded step 41.6 -> 44.2 us).
+      dense_ok = nb && novf[0] == 0 && novf[1] == 0 && d.Nc <= (1 << 24) &&
+                 (e->tun.hist_dense ? e->tun.hist_dense == 2 : (d.kind == VC_KIND_VFULL && e->tail_kind == 2));
+      for (int m = 0; m < (vel ? 2 : 1); ++m) {
+        HIPCHK(e, hipMemcpy(htab.data(), tab[m], htab.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+        if (dense_ok) vc_build_dense_hist(htab.data(), d.Ng, d.Ng_pad, hc, hc_off, hc_rows);
+        std::vector<float> ov(novf[m]);
+        std::vector<int> og(novf[m]);
+        if (novf[m]) {
+          HIPCHK(e, hipMemcpy(ov.data(), ovf_val[m], novf[m] * sizeof(float), hipMemcpyDeviceToHost));
+          HIPCHK(e, hipMemcpy(og.data(), ovf_gene[m], novf[m] * sizeof(int), hipMemcpyDeviceToHost));
         }
-        if (!vel) for (int g = 0; g < d.Ng; ++g) ptr.push_back((int)val.size());
-        e->hist_on_device = 1;
-      } else {
-        // checker path (tuning.host_hist) or fallback: histograms from a host copy of the raw counts
-        if (e->hS.empty()) {
-          if (e->src[0].kind != 1) { free_transients(); return e->fail(VC_ERR_UNSUPPORTED, "CSR input with more than %u non-integer / large counts per matrix", OVF_CAP); }
-          const size_t span = (size_t)(d.Ng - 1) * e->dgs + (size_t)(d.Nc - 1) * e->dcs + 1;
-          e->hS.resize(span);
-          HIPCHK(e, hipMemcpy(e->hS.data(), e->src[0].dense, span * sizeof(float), hipMemcpyDeviceToHost));
-          if (vel) { e->hU.resize(span); HIPCHK(e, hipMemcpy(e->hU.data(), e->src[1].dense, span * sizeof(float), hipMemcpyDeviceToHost)); }
-          e->gs = e->dgs; e->cs = e->dcs;
-        }
-        lg_S = vc_build_hist_host(e->hS.data(), e->gs, e->cs, d.Ng, d.Nc, ptr, val, cnt, &bad_host);
-        if (vel) lg_U = vc_build_hist_host(e->hU.data(), e->gs, e->cs, d.Ng, d.Nc, ptr, val, cnt, &bad_host);
-        else for (int g = 0; g < d.Ng; ++g) ptr.push_back((int)val.size());
-        e->hist_on_device = 0;
-        if (bad_host) { free_transients(); return e->fail(VC_ERR_ARG, "count matrices must be finite and >= 0 (NaN / Inf / negative value found)"); }
+        std::vector<std::pair<int, float>> ovf(novf[m]);
+        for (unsigned i = 0; i < novf[m]; ++i) ovf[i] = {og[i], ov[i]};
+        const double lg = vc_compact_hist(htab.data(), d.Ng, ovf, ptr, val, cnt);
+        (m == 0 ? s.lg_S : s.lg_U) = lg;
       }
+      if (!vel) for (int g = 0; g < d.Ng; ++g) ptr.push_back((int)val.size());
+      e->hist_on_device = 1;
     } else {
-      ptr.assign(2 * (size_t)d.Ng, 0);
-    }
-    ptr.push_back((int)val.size());
-    free_transients();
-    for (auto& c : e->src) c.release();
-    e->setup_transient_bytes = transient;
-    // tasks: runs of <= 64 histogram entries of one gene and matrix, sorted by gene
-    std::vector<int> task, tptr;
-    d.hist_dense = dense_ok ? 1 : 0;
-    if (dense_ok) {
-      // one task per gene and matrix, in that order: what role 12 / the loss block / K_post add up per gene is unchanged
-      const int nm = vel ? 2 : 1, nblk = d.Ng_pad / 64;
-      for (int g = 0; g < d.Ng; ++g) {
-        tptr.push_back(nm * g);
-        for (int m = 0; m < nm; ++m) task.insert(task.end(), {g, m, 0, 0});
+      // checker path (tuning.host_hist) or fallback: histograms from a host copy of the raw counts
+      if (e->hS.empty()) {
+        if (e->src[0].kind != 1) return e->fail(VC_ERR_UNSUPPORTED, "CSR input with more than %u non-integer / large counts per matrix", OVF_CAP);
+        const size_t span = (size_t)(d.Ng - 1) * e->dgs + (size_t)(d.Nc - 1) * e->dcs + 1;
+        e->hS.resize(span);
+        HIPCHK(e, hipMemcpy(e->hS.data(), e->src[0].dense, span * sizeof(float), hipMemcpyDeviceToHost));
+        if (vel) { e->hU.resize(span); HIPCHK(e, hipMemcpy(e->hU.data(), e->src[1].dense, span * sizeof(float), hipMemcpyDeviceToHost)); }
+        e->gs = e->dgs; e->cs = e->dcs;
       }
-      tptr.push_back(nm * d.Ng);
-      if (!vel) {                               // the U half of the tables: empty
-        hc_off.resize(2 * (size_t)nblk, (int)(hc.size() / 64));
-        hc_rows.resize(2 * (size_t)nblk, 0);
-      }
-      hc.resize(hc.size() + 64, 0.f);          // (a row of padding: the prefetch of an empty block reads row 0)
-      // gene blocks that hold a highly expressed gene: the one-launch tail gives each of them four quarter blocks (16 genes, one wave per
-      // SIMD of a CU of their own: vc_common.h, vc_hist_dense16_finish<true>), every quarter to ITS genes' largest count
-      std::vector<int> hc_rows_q(hc_rows.size() * 4, 0), hc_split;
-      for (size_t i = 0; i < hc_rows.size(); ++i) {
-        for (int qd = 0; qd < 4; ++qd) {
-          int rq = 0;
-          for (int j = hc_rows[i] - 1; j >= 0 && !rq; --j)
-            for (int l = 16 * qd; l < 16 * qd + 16; ++l)
-              if (hc[((size_t)hc_off[i] + j) * 64 + l] != 0.f) { rq = j + 1; break; }
-          hc_rows_q[i * 4 + qd] = rq;
-        }
-        if (hc_rows[i] > VC_HIST_SPLIT_ROWS) hc_split.push_back((int)i);
-      }
-      b.n_hc_split = (int)hc_split.size();
-      if (hc_split.empty()) hc_split.push_back(0);
-      TRY(upload(e, hc, &b.HC));
-      TRY(upload(e, hc_off, &b.hc_off));
-      TRY(upload(e, hc_rows, &b.hc_rows));
-      TRY(upload(e, hc_rows_q, &b.hc_rows_q));
-      TRY(upload(e, hc_split, &b.hc_split));
-    } else {
-      vc_build_hist_tasks(ptr, d.Ng, task, tptr);
-      b.HC = nullptr; b.hc_off = nullptr; b.hc_rows = nullptr; b.hc_rows_q = nullptr; b.hc_split = nullptr; b.n_hc_split = 0;
+      s.lg_S = vc_build_hist_host(e->hS.data(), e->gs, e->cs, d.Ng, d.Nc, ptr, val, cnt, &bad_host);
+      if (vel) s.lg_U = vc_build_hist_host(e->hU.data(), e->gs, e->cs, d.Ng, d.Nc, ptr, val, cnt, &bad_host);
+      else for (int g = 0; g < d.Ng; ++g) ptr.push_back((int)val.size());
+      e->hist_on_device = 0;
+      if (bad_host) return e->fail(VC_ERR_ARG, "count matrices must be finite and >= 0 (NaN / Inf / negative value found)");
     }
-    b.n_tasks = (int)task.size() / 4;
-    TRY(upload(e, task, &b.h_task));
-    TRY(upload(e, tptr, &b.h_tptr));
-    TRY(e->dalloc(&b.HL, 2 * (size_t)std::max(1, b.n_tasks)));       // two halves: by the parity of the sample's step (d.hist_par)
-    TRY(e->dalloc(&b.HD, 2 * (size_t)std::max(1, b.n_tasks)));
-    HIPCHK(e, hipMemset(b.HL, 0, 2 * sizeof(double) * std::max(1, b.n_tasks)));
-    HIPCHK(e, hipMemset(b.HD, 0, 2 * sizeof(double) * std::max(1, b.n_tasks)));
-    TRY(upload(e, ptr, &b.h_ptr));
-    TRY(upload(e, val, &b.h_val));
-    TRY(upload(e, cnt, &b.h_cnt));
-    e->h_ptr_host = ptr; e->h_val_host = val; e->h_cnt_host = cnt;
-    {
-      // sum_c k_U per gene (this rank's cells): the S+U kernel adds -log beta * sum_c k_U once per gene instead of subtracting
-      // log beta from eta_U once per (gene, cell) (VC_HOIST_LB)
-      std::vector<float> gsu((size_t)d.Ng_pad, 0.f);
-      if (vel && want_hist)
-        for (int g = 0; g < d.Ng; ++g) {
-          double sum = 0.0;
-          for (int j = ptr[(size_t)d.Ng + g]; j < ptr[(size_t)d.Ng + g + 1]; ++j) sum += (double)val[j] * (double)cnt[j];
-          gsu[g] = (float)sum;
-        }
-      TRY(upload(e, gsu, &b.gene_sum_u));
-    }
-    std::vector<float>().swap(e->hS);
-    std::vector<float>().swap(e->hU);
+  } else {
+    ptr.assign(2 * (size_t)d.Ng, 0);
   }
-  const double ln_const_s = (double)d.Ng * d.Nc * (std::log((double)d.sigma_ln_s) + 0.5 * std::log(2.0 * M_PI));
-  const double ln_const_u = (double)d.Ng * d.Nc * (std::log((double)d.sigma_ln_u) + 0.5 * std::log(2.0 * M_PI));
-  auto obs_const = [&](bool is_u) {   // constant part of -loglik of one matrix
-    if (d.noise == VC_NOISE_LOGNORMAL) return is_u ? ln_const_u : ln_const_s;
-    return is_u ? lg_U : lg_S;
-  };
+  ptr.push_back((int)val.size());
+  s.scratch.release();
+  for (auto& c : e->src) c.release();
+  e->setup_transient_bytes = s.scratch.bytes + s.transient;
+  // tasks: runs of <= 64 histogram entries of one gene and matrix, sorted by gene
+  std::vector<int> task, tptr;
+  d.hist_dense = dense_ok ? 1 : 0;
+  if (dense_ok) {
+    // one task per gene and matrix, in that order: what role 12 / the loss block / K_post add up per gene is unchanged
+    const int nm = vel ? 2 : 1, nblk = d.Ng_pad / 64;
+    for (int g = 0; g < d.Ng; ++g) {
+      tptr.push_back(nm * g);
+      for (int m = 0; m < nm; ++m) task.insert(task.end(), {g, m, 0, 0});
+    }
+    tptr.push_back(nm * d.Ng);
+    if (!vel) {                               // the U half of the tables: empty
+      hc_off.resize(2 * (size_t)nblk, (int)(hc.size() / 64));
+      hc_rows.resize(2 * (size_t)nblk, 0);
+    }
+    hc.resize(hc.size() + 64, 0.f);          // (a row of padding: the prefetch of an empty block reads row 0)
+    // gene blocks that hold a highly expressed gene: the one-launch tail gives each of them four quarter blocks (16 genes, one wave per
+    // SIMD of a CU of their own: vc_common.h, vc_hist_dense16_finish<true>), every quarter to ITS genes' largest count
+    std::vector<int> hc_rows_q(hc_rows.size() * 4, 0), hc_split;
+    for (size_t i = 0; i < hc_rows.size(); ++i) {
+      for (int qd = 0; qd < 4; ++qd) {
+        int rq = 0;
+        for (int j = hc_rows[i] - 1; j >= 0 && !rq; --j)
+          for (int l = 16 * qd; l < 16 * qd + 16; ++l)
+            if (hc[((size_t)hc_off[i] + j) * 64 + l] != 0.f) { rq = j + 1; break; }
+        hc_rows_q[i * 4 + qd] = rq;
+      }
+      if (hc_rows[i] > VC_HIST_SPLIT_ROWS) hc_split.push_back((int)i);
+    }
+    b.n_hc_split = (int)hc_split.size();
+    if (hc_split.empty()) hc_split.push_back(0);
+    TRY(upload(e, hc, &b.HC));
+    TRY(upload(e, hc_off, &b.hc_off));
+    TRY(upload(e, hc_rows, &b.hc_rows));
+    TRY(upload(e, hc_rows_q, &b.hc_rows_q));
+    TRY(upload(e, hc_split, &b.hc_split));
+  } else {
+    vc_build_hist_tasks(ptr, d.Ng, task, tptr);
+    b.HC = nullptr; b.hc_off = nullptr; b.hc_rows = nullptr; b.hc_rows_q = nullptr; b.hc_split = nullptr; b.n_hc_split = 0;
+  }
+  b.n_tasks = (int)task.size() / 4;
+  TRY(upload(e, task, &b.h_task));
+  TRY(upload(e, tptr, &b.h_tptr));
+  TRY(e->dalloc(&b.HL, 2 * (size_t)std::max(1, b.n_tasks)));       // two halves: by the parity of the sample's step (d.hist_par)
+  TRY(e->dalloc(&b.HD, 2 * (size_t)std::max(1, b.n_tasks)));
+  HIPCHK(e, hipMemset(b.HL, 0, 2 * sizeof(double) * std::max(1, b.n_tasks)));
+  HIPCHK(e, hipMemset(b.HD, 0, 2 * sizeof(double) * std::max(1, b.n_tasks)));
+  TRY(upload(e, ptr, &b.h_ptr));
+  TRY(upload(e, val, &b.h_val));
+  TRY(upload(e, cnt, &b.h_cnt));
+  e->h_ptr_host = ptr; e->h_val_host = val; e->h_cnt_host = cnt;
+  {
+    // sum_c k_U per gene (this rank's cells): the S+U kernel adds -log beta * sum_c k_U once per gene instead of subtracting
+    // log beta from eta_U once per (gene, cell) (VC_HOIST_LB)
+    std::vector<float> gsu((size_t)d.Ng_pad, 0.f);
+    if (vel && s.want_hist)
+      for (int g = 0; g < d.Ng; ++g) {
+        double sum = 0.0;
+        for (int j = ptr[(size_t)d.Ng + g]; j < ptr[(size_t)d.Ng + g + 1]; ++j) sum += (double)val[j] * (double)cnt[j];
+        gsu[g] = (float)sum;
+      }
+    TRY(upload(e, gsu, &b.gene_sum_u));
+  }
+  std::vector<float>().swap(e->hS);
+  std::vector<float>().swap(e->hU);
+  return VC_OK;
+}
+
+// The step-invariant constant of the loss, with the S likelihood hoisted out of the steps for the U-only kernel, and the histogram
+// sums evaluated once when shape_inv is conditioned
+static int fin_constant_loss(vc_engine* e, FinalizeState& s) {
+  VcDims& d = e->d;
+  VcBufs& b = e->b;
+  hipStream_t st = s.st;
+  const bool vel = d.model == VC_MODEL_VELOCITY;
+  const bool nb = d.noise == VC_NOISE_NB;
+  // constant part of -loglik of each matrix
+  const bool ln = d.noise == VC_NOISE_LOGNORMAL;
+  const double obs_s = ln ? (double)d.Ng * d.Nc * (std::log((double)d.sigma_ln_s) + 0.5 * std::log(2.0 * M_PI)) : s.lg_S;
+  const double obs_u = ln ? (double)d.Ng * d.Nc * (std::log((double)d.sigma_ln_u) + 0.5 * std::log(2.0 * M_PI)) : s.lg_U;
   double cl = 0.0;
-  if (d.kind != VC_KIND_VU) cl += obs_const(false);
-  if (vel) cl += obs_const(true);
+  if (d.kind != VC_KIND_VU) cl += obs_s;
+  if (vel) cl += obs_u;
 
   if (d.kind == VC_KIND_VU) {
     // hoist the S likelihood: with phi, nu, dnu, shape_inv fixed it does not change between steps
     VcDims d2 = d;
-    d2.kind = VC_KIND_PHASE; d2.nq = nq_of(VC_KIND_PHASE); d2.nco = 1;
+    d2.kind = VC_KIND_PHASE; d2.nq = nq_of(d, VC_KIND_PHASE); d2.nco = 1;
     d2.pw_inline = 0; d2.pw_slots = 0;
     d2.hist_has_S = nb; d2.hist_has_U = 0;
     vc_launch_pre(d2, b, nullptr, nullptr, 0, 0, nullptr, 1, nb ? 1 : 0, st);
@@ -1366,7 +1413,7 @@ static int finalize_impl(vc_engine* e, void* hip_stream) {
     HIPCHK(e, hipMemcpy(lo.data(), b.LO, sizeof(float) * d.n_main_wg, hipMemcpyDeviceToHost));
     HIPCHK(e, hipMemcpy(rrow.data(), b.GT + (size_t)(d.K + 2) * d.Ng_pad, sizeof(float) * d.Ng, hipMemcpyDeviceToHost));
     if (nb) HIPCHK(e, hipMemcpy(hl.data(), b.HL, sizeof(double) * b.n_tasks, hipMemcpyDeviceToHost));
-    double sconst = obs_const(false);
+    double sconst = obs_s;
     for (float v : lo) sconst -= (double)v;
     if (nb) {
       for (int g = 0; g < d.Ng; ++g) sconst -= (double)d.Nc * rrow[g] * std::log((double)rrow[g]);
@@ -1382,27 +1429,53 @@ static int finalize_impl(vc_engine* e, void* hip_stream) {
   b.const_loss = cl;
   HIPCHK(e, hipStreamSynchronize(st));
   HIPCHK(e, hipGetLastError());
+  return VC_OK;
+}
+
+static int finalize_impl(vc_engine* e, void* hip_stream) {
+  TRY(fin_check_inputs(e));
+  e->finalize_started = true;
+  FinalizeState s;                      // (its set-up scratch is freed on every way out of here)
+  s.st = (hipStream_t)hip_stream;
+  fin_batch_plan(e, s);
+  TRY(fin_choose_kernel(e, s));
+  TRY(fin_pack_counts(e, s));
+  TRY(fin_tiling(e, s));
+  TRY(fin_step_buffers(e));
+  TRY(fin_histograms(e, s));
+  TRY(fin_constant_loss(e, s));
   // the instantiation of the small kernels compiled for this configuration, if there is one (vc_tail_spec.h)
-  d.spec = e->tun.no_tail_spec ? VC_SPEC_NONE : vc_spec_match(d);
+  e->d.spec = e->tun.no_tail_spec ? VC_SPEC_NONE : vc_spec_match(e->d);
   e->finalized = true;
   std::vector<float>().swap(e->hD);
   std::vector<float>().swap(e->hDb);   // kept until here: every failure above leaves the batch design matrix in place
   return VC_OK;
 }
 
+// One likelihood launch of a step; with vc_set_timing on, between the two events of a pair of the pool (bench.py roofline)
+static int launch_main(vc_engine* e, vc_main_launch_fn fn, const VcDims& d, const VcBufs& b, hipStream_t st) {
+  if (!e->timing) { fn(d, b, st); return VC_OK; }
+  if (e->ev_used == e->ev_pool.size()) TRY(e->drain_events());
+  auto& pr = e->ev_pool[e->ev_used++];
+  HIPCHK(e, hipEventRecord(pr.first, st));
+  fn(d, b, st);
+  HIPCHK(e, hipEventRecord(pr.second, st));
+  return VC_OK;
+}
+
+// e->b as K_main of the fused steps sees it: it advances the device step counter and leaves the optimiser's step size behind
+static VcBufs fused_bufs(const vc_engine* e, int64_t* step_dev, const VcAdamArgs& a) {
+  VcBufs b2 = e->b;
+  b2.step_ctr = (long long*)step_dev;
+  b2.adam_lr0 = a.lr0; b2.adam_lrd_l = a.lrd_l; b2.adam_b1l = a.b1l; b2.adam_b2l = a.b2l; b2.adam_kind = a.kind;
+  return b2;
+}
+
 static int launch_front(vc_engine* e, const float* params, const float* eps, uint64_t seed, int64_t step,
                         int64_t* step_dev, float* grad, hipStream_t st) {
   vc_launch_pre(e->d, e->b, params, eps, seed, (long long)step, (const long long*)step_dev, 0,
                 e->hist_each_step ? 1 : 0, st);
-  if (e->timing) {
-    if (e->ev_used == e->ev_pool.size()) TRY(e->drain_events());
-    auto& pr = e->ev_pool[e->ev_used++];
-    HIPCHK(e, hipEventRecord(pr.first, st));
-    e->main_fn(e->d, e->b, st);
-    HIPCHK(e, hipEventRecord(pr.second, st));
-  } else {
-    e->main_fn(e->d, e->b, st);
-  }
+  TRY(launch_main(e, e->main_fn, e->d, e->b, st));
   vc_launch_post(e->d, e->b, params, grad, (long long*)step_dev, st);
   return VC_OK;
 }
@@ -1449,23 +1522,6 @@ extern "C" int vc_svi_step(vc_engine* e, float* params, const float* eps, uint64
   return VC_OK;
 }
 
-// Which launch follows K_main in the steady state of vc_svi_run_fused: 1 = the tutorial flow's merged tail (vc_launch_tail_merged),
-// 2 = the one-launch tail of every other single-rank step that has what it needs (vc_launch_tail2), 0 = K_tail + K_omega
-static int fused_tail_kind(const vc_engine* e) {
-  if (e->d.generic) return 0;
-  const bool with_hist = e->hist_each_step;
-  bool merged = e->d.pw_inline && e->d.kind == VC_KIND_VU && !with_hist && (e->d.cond >> VC_SITE_PHIXY & 1u);
-  if (e->tun.no_tail_merged) merged = false;
-  if (merged) return 1;
-  // Round 4: every other single-rank step in TWO launches as well -- the phase model (no nu_omega chain), and the velocity
-  // models whenever K_main supplies the partials of d loglik / d nu_omega itself (pw_inline), so that the chain runs inside the
-  // cell blocks.  tuning.no_tail2 keeps the three-launch step (A/B, tests: the same bits).
-  bool tail2 = e->cfg.world_size == 1 && (e->d.model == VC_MODEL_PHASE || e->d.pw_inline != 0);
-  if (e->tun.no_tail2) tail2 = false;
-  return tail2 ? 2 : 0;
-}
-static int fused_launches_per_step(const vc_engine* e) { return fused_tail_kind(e) ? 2 : 3; }
-
 extern "C" int vc_svi_run_fused(vc_engine* e, float* params, uint64_t seed, int64_t* step_dev, float* grad,
                                 double* loss_dev, int64_t loss_slots, float* exp_avg, float* exp_avg_sq, double lr,
                                 double lrd, double beta1, double beta2, double adam_eps, double clip_norm, int prime,
@@ -1491,27 +1547,17 @@ extern "C" int vc_svi_run_fused(vc_engine* e, float* params, uint64_t seed, int6
     vc_launch_omega(e->d, e->b, params, grad, sd, seed, a, loss_dev, (long long)loss_slots, 1, with_hist, st);
     e->plain_steps = 0;
   }
-  VcBufs b2 = e->b;
-  b2.step_ctr = (long long*)step_dev;
-  b2.adam_lr0 = a.lr0; b2.adam_lrd_l = a.lrd_l; b2.adam_b1l = a.b1l; b2.adam_b2l = a.b2l; b2.adam_kind = a.kind;
+  const VcBufs b2 = fused_bufs(e, step_dev, a);
   // Tutorial flow (U-only kernel with its own nu_omega partials, no histogram terms per step): from the third step after the
   // tables were primed, K_tail's gene blocks and K_omega's blocks go out as ONE launch (vc_launch_tail_merged: why that is
   // safe); the first two steps fill both halves of the loss terms the absent cell blocks would have written.
-  const int tail_kind = fused_tail_kind(e);
+  const int tail_kind = e->tail_kind;
   const bool merged = tail_kind == 1, tail2 = tail_kind == 2;
   for (int64_t i = 0; i < n_steps; ++i) {
     // vc_set_loss_every(k > 1): the gradient-only kernel except at every k-th likelihood launch
     const vc_main_launch_fn fn = (e->loss_every > 1 && e->main_fn_nl && (e->loss_ctr % e->loss_every) != 0) ? e->main_fn_nl : e->main_fn;
     ++e->loss_ctr;
-    if (e->timing) {
-      if (e->ev_used == e->ev_pool.size()) TRY(e->drain_events());
-      auto& pr = e->ev_pool[e->ev_used++];
-      HIPCHK(e, hipEventRecord(pr.first, st));
-      fn(e->d, b2, st);
-      HIPCHK(e, hipEventRecord(pr.second, st));
-    } else {
-      fn(e->d, b2, st);
-    }
+    TRY(launch_main(e, fn, e->d, b2, st));
     if (merged && e->plain_steps >= 2) {
       vc_launch_tail_merged(e->d, e->b, params, grad, sd, seed, a, loss_dev, (long long)loss_slots, st);
     } else if (tail2) {
@@ -1589,15 +1635,7 @@ extern "C" int vc_svi_run_particles(vc_engine* e, float* params, uint64_t seed, 
     vc_launch_pre_particles(e->d, e->b, e->particle_bufs_dev, params, seed, (const long long*)step_dev, e->hist_each_step ? 1 : 0, K, st);
     for (int k = 0; k < K; ++k) {
       const VcBufs& b = k == 0 ? e->b : e->particles[(size_t)k - 1].b;
-      if (e->timing) {
-        if (e->ev_used == e->ev_pool.size()) TRY(e->drain_events());
-        auto& pr = e->ev_pool[e->ev_used++];
-        HIPCHK(e, hipEventRecord(pr.first, st));
-        e->main_fn(e->d, b, st);
-        HIPCHK(e, hipEventRecord(pr.second, st));
-      } else {
-        e->main_fn(e->d, b, st);
-      }
+      TRY(launch_main(e, e->main_fn, e->d, b, st));
     }
     vc_launch_post_particles(e->d, e->b, e->particle_bufs_dev, pg, params, st);
     vc_launch_particle_fin_adam(e->d, e->particle_bufs_dev, pg, params, loss_dev, (long long)loss_slots, (long long)(step0 + i),
@@ -1619,15 +1657,7 @@ extern "C" int vc_svi_run_particles(vc_engine* e, float* params, uint64_t seed, 
       hipStream_t sk = (k == 0 || serial) ? st : e->particles[k - 1].st;
       vc_launch_pre(e->d, b, params, nullptr, seed, 0, (const long long*)step_dev, 0, e->hist_each_step ? 1 : 0, sk, K, k);
       if (k > 0 && !serial) HIPCHK(e, hipStreamWaitEvent(sk, k == 1 ? e->ev_main0 : e->particles[k - 2].main_done, 0));
-      if (e->timing) {
-        if (e->ev_used == e->ev_pool.size()) TRY(e->drain_events());
-        auto& pr = e->ev_pool[e->ev_used++];
-        HIPCHK(e, hipEventRecord(pr.first, sk));
-        e->main_fn(e->d, b, sk);
-        HIPCHK(e, hipEventRecord(pr.second, sk));
-      } else {
-        e->main_fn(e->d, b, sk);
-      }
+      TRY(launch_main(e, e->main_fn, e->d, b, sk));
       if (k + 1 < K && !serial) HIPCHK(e, hipEventRecord(k == 0 ? e->ev_main0 : e->particles[k - 1].main_done, sk));
       // (the step counter advances once per step, behind the average: no K_post touches it)
       vc_launch_post(e->d, b, params, pg.g[k], nullptr, sk);
@@ -1817,9 +1847,7 @@ extern "C" int vc_svi_run_sharded(vc_engine* e, float* params, uint64_t seed, in
     vc_launch_tail(ds, e->b, params, grad, sd, seed, a, 1, 0, VcXb{}, st);
     vc_launch_omega(ds, e->b, params, grad, sd, seed, a, loss_dev, (long long)loss_slots, 1, with_hist, st);
   }
-  VcBufs b2 = e->b;
-  b2.step_ctr = (long long*)step_dev;
-  b2.adam_lr0 = a.lr0; b2.adam_lrd_l = a.lrd_l; b2.adam_b1l = a.b1l; b2.adam_b2l = a.b2l; b2.adam_kind = a.kind;
+  const VcBufs b2 = fused_bufs(e, step_dev, a);
   // Round 6, opt-in (vc_tuning.p2p_one_launch with the peer-to-peer exchange): phases A and B in ONE launch, the exchange at block
   // granularity inside it (vc_tail_x_kernel).  Admitted where every block that may spin on another is resident at one 1024-thread block
   // per CU -- gene blocks + the cell blocks of the widest shard + the loss block <= 240 -- and the cell blocks are K_omega's (256 cells).
@@ -1827,15 +1855,7 @@ extern "C" int vc_svi_run_sharded(vc_engine* e, float* params, uint64_t seed, in
                           ds.nb_post_gene + e->xb_pw_cap + 1 <= 240 && ds.nb_tail_cell <= e->xb_pw_cap;
   for (int64_t i = 0; i < n_steps; ++i) {
     if (one_launch) {
-      if (e->timing) {
-        if (e->ev_used == e->ev_pool.size()) TRY(e->drain_events());
-        auto& pr = e->ev_pool[e->ev_used++];
-        HIPCHK(e, hipEventRecord(pr.first, st));
-        main_fn(ds, b2, st);
-        HIPCHK(e, hipEventRecord(pr.second, st));
-      } else {
-        main_fn(ds, b2, st);
-      }
+      TRY(launch_main(e, main_fn, ds, b2, st));
       const size_t slot_off = (size_t)e->p2p.flag_words + (size_t)(e->p2p_step & 1) * (size_t)e->p2p.slot_floats;
       VcXb xw = xb, xr = xb;
       xw.x = reinterpret_cast<float*>(e->p2p_own) + slot_off;
@@ -1851,15 +1871,7 @@ extern "C" int vc_svi_run_sharded(vc_engine* e, float* params, uint64_t seed, in
       continue;
     }
     if (phase != VC_PHASE_B) {
-      if (e->timing) {
-        if (e->ev_used == e->ev_pool.size()) TRY(e->drain_events());
-        auto& pr = e->ev_pool[e->ev_used++];
-        HIPCHK(e, hipEventRecord(pr.first, st));
-        main_fn(ds, b2, st);
-        HIPCHK(e, hipEventRecord(pr.second, st));
-      } else {
-        main_fn(ds, b2, st);
-      }
+      TRY(launch_main(e, main_fn, ds, b2, st));
       VcXb xa = xb;
       if (use_p2p)        // phase A writes this rank's slot of the step's parity; K_xchg sums every rank's slot into xbuf
         xa.x = reinterpret_cast<float*>(e->p2p_own) + e->p2p.flag_words + (size_t)(e->p2p_step & 1) * (size_t)e->p2p.slot_floats;
@@ -1871,8 +1883,6 @@ extern "C" int vc_svi_run_sharded(vc_engine* e, float* params, uint64_t seed, in
       // Round 6: the exchange FOLDED into phase B -- no launch for the sum: phase B's blocks pass the exchange's gate themselves
       // (block 0 publishes and waits; the kernel boundary behind phase A released this rank's slot) and add the ranks' slots of this
       // step's parity where they read them, in rank order (vc_xget: the bits of the separate kernel).  K_main -> phase A -> phase B.
-      const size_t slot_off = (size_t)e->p2p.flag_words + (size_t)(e->p2p_step & 1) * (size_t)e->p2p.slot_floats;
-      (void)slot_off;
       xbb.nslots = e->p2p.world;
       xbb.slots = reinterpret_cast<const float* const*>(e->p2p_tab) + VC_P2P_MAX_RANKS * (1 + (int)(e->p2p_step & 1));
       gate.regions = reinterpret_cast<void* const*>(e->p2p_tab); gate.world = e->p2p.world; gate.rank = e->p2p.rank;
@@ -2000,7 +2010,7 @@ extern "C" int vc_get_stats(const vc_engine* e, vc_stats* out) {
   out->hist_on_device = e->hist_on_device;
   out->setup_transient_bytes = (int64_t)e->setup_transient_bytes;
   for (int p = 0; p < 4; ++p) out->pass_cells[p] = d.pass_cw[p];
-  out->launches_per_step = fused_launches_per_step(e);
+  out->launches_per_step = e->tail_kind ? 2 : 3;
   out->pw_inline = d.pw_inline;
   out->generic = d.generic;
   snprintf(out->main_kernel_name, sizeof out->main_kernel_name, "vc_main_kernel<%d,%d,%s,gpl%d%s%s>", d.H, d.nbk, e->main_name, d.gpl,
@@ -2011,7 +2021,7 @@ extern "C" int vc_get_stats(const vc_engine* e, vc_stats* out) {
   // pw_inline matches a "*_rank" row and still runs the run-time-flag kernels) -- report what runs, and the match beside it.
   int speck = 0;
   if (e->cfg.world_size > 1) speck = VC_SPECK_SHARDED;
-  else { const int tk = fused_tail_kind(e); speck = tk == 1 ? VC_SPECK_MERGED : (tk == 2 ? VC_SPECK_TAIL2 : 0); }
+  else speck = e->tail_kind == 1 ? VC_SPECK_MERGED : (e->tail_kind == 2 ? VC_SPECK_TAIL2 : 0);
   const int used = (d.spec > 0 && (VC_SPECS[d.spec].kind & speck)) ? d.spec : VC_SPEC_NONE;
   out->pw_lane = d.pw_lane;
   out->hist_split = d.hist_dense ? e->b.n_hc_split : 0;

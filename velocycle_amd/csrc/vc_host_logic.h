@@ -278,6 +278,29 @@ static inline bool vc_order_by_batch(const std::vector<int>& bid, int Nb, std::v
   return sorted;
 }
 
+// The condition of every batch when the condition design D (Nx, Nc, row-major) is one-hot and constant within every batch (bid: the
+// batch of every cell, vc_onehot_batches): cond[q] = the condition of batch q's cells, 0 for a batch without cells.  Otherwise
+// cond is left empty and the result is false.
+static inline bool vc_batch_conditions(const float* D, int Nx, long long Nc, const std::vector<int>& bid, int Nb, std::vector<int>& cond) {
+  cond.assign((size_t)Nb, -1);
+  bool ok = Nx >= 1;
+  for (long long c = 0; c < Nc && ok; ++c) {
+    int xc = -1;
+    for (int x = 0; x < Nx; ++x) {
+      const float v = D[(size_t)x * Nc + c];
+      if (v == 1.f && xc < 0) xc = x;
+      else if (v != 0.f) ok = false;
+    }
+    if (xc < 0) ok = false;
+    int& bc = cond[(size_t)bid[(size_t)c]];
+    if (bc < 0) bc = xc;
+    else if (bc != xc) ok = false;
+  }
+  for (int& v : cond) if (v < 0) v = 0;
+  if (!ok) cond.clear();
+  return ok;
+}
+
 // The workgroup table of the likelihood kernel {first cell, cells per wave, batch, end} with every workgroup inside one batch
 // (cells = positions; batch q holds positions [sum len[<q], + len[q])).  The chunks of a gene block keep their nominal weights
 // (pass_cw of their dispatch pass: the unequal shares of vc_tile_cells); consecutive groups of chunks are given to the batches
