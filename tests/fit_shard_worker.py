@@ -2,8 +2,11 @@
 fit, BASELINE.json configs[4]) through the PUBLIC entry points, run either as one process or as the ranks of a
 torch.distributed job with the cells sharded.  Every rank builds the same full-size inputs; rank 0 writes the results.
 
-  python tests/fit_shard_worker.py OUT.npz MODE        MODE = perf | parity
-  python -m torch.distributed.run --nproc-per-node 2 ... tests/fit_shard_worker.py OUT.npz MODE
+  python tests/fit_shard_worker.py OUT.npz MODE [--plant-overflow]        MODE = perf | parity
+  python -m torch.distributed.run --nproc-per-node 2 ... tests/fit_shard_worker.py OUT.npz MODE [--plant-overflow]
+
+--plant-overflow: one spliced and one unspliced count of 70 000 in a cell of the second half of the cells (rank 1's shard of a
+2-rank run): that shard stores its counts as float32, the other as uint16.
 
 Test hook VC_BENCH_ONE_DEVICE=1: every rank on cuda:0 and gloo instead of RCCL (a 1-GPU box cannot host two RCCL ranks)."""
 import os
@@ -18,6 +21,7 @@ import torch  # noqa: E402
 
 def main():
     out_path, mode = sys.argv[1], sys.argv[2]
+    plant = "--plant-overflow" in sys.argv[3:]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     one_device = os.environ.get("VC_BENCH_ONE_DEVICE", "0") == "1"
@@ -40,7 +44,10 @@ def main():
 
     ncell, ngene, n1, n2 = 1501, 150, 30, 30            # 2 samples x 1501 cells: odd total -> unequal shards
     sp = make_velocity_spec(ncell, ngene, "vjoint", n_conditions=2, Hw=0, seed=12)
-    ad = AnnDataLite(sp.S.t().numpy(), sp.U.t().numpy())
+    S_cm, U_cm = sp.S.t().numpy().copy(), sp.U.t().numpy().copy()
+    if plant:
+        S_cm[2 * ncell - 2, 5] = U_cm[2 * ncell - 2, 7] = 70000.0
+    ad = AnnDataLite(S_cm, U_cm)
     ad.obs["batch"] = [f"d{int(b)}" for b in sp.truth["batch"]]
     cyc = C.Cycle.from_array(sp.mu_nu.T.numpy(), sp.sd_nu.T.numpy(), list(ad.var.index))
     ph = C.Phases.from_array(sp.phixy_prior.T.numpy(), cell_names=list(ad.obs.index))
@@ -72,6 +79,8 @@ def main():
     vf.fit(opt(n2), num_steps=n2, verbose=False, mode=mode, seed=22)
     res["vel_losses"] = np.array(vf.losses)
     res["vel_kernel"] = np.array(vf.engine.stats["main_kernel"])
+    res["phase_storage"] = np.array(pf.engine.stats["count_storage"])
+    res["vel_storage"] = np.array(vf.engine.stats["count_storage"])
     for a in ("phis_pyro", "fourier_coef", "disp_pyro", "log_betas", "log_gammas", "velocity_coef"):
         res["vel_" + a] = np.asarray(getattr(vf, a))
     res["vel_loc"] = pyro.param("loc").numpy()

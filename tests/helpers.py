@@ -218,3 +218,128 @@ def assert_params_track_oracle(got, par64, par32, frac=0.99, report=None):
         print(f"\n[{report}] per block: fraction within tolerance, max |err| / max-norm (HIP | float32 oracle): "
               + ", ".join(f"{k} {a:.4f} {b:.1e} | {c:.4f} {d:.1e}" for k, (a, b, c, d) in out.items()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Boundary counts: the per-gene count histograms behind every lgamma / digamma term of the negative binomial have their own
+# special cases (vc_host_logic.h: dense tail-count tables for integer counts < 2048; vc_common.h: the first 256 levels
+# prefetched, levels 256 .. 639 read only by blocks past 256, a second loop from 640, quarter blocks for blocks past 256 levels;
+# the (value, multiplicity) lists with the Stirling difference as soon as one count is >= 2048 or not an integer; uint16 count
+# storage while every count is an integer <= 65535).  These data put genes at those boundaries.
+# ---------------------------------------------------------------------------------------------------------------------
+BOUNDARY_LEVELS = (255, 256, 257, 639, 640, 641, 2047)
+# the per-gene bar of the shape_inv_locs gradient: |got - float64| <= GENE_RTOL x the gene's sum of absolute terms
+# (nb_shape_inv_terms); tests/test_count_extremes_cpu.py checks that one count level more or less moves it by > 3 GENE_RTOL
+GENE_RTOL = 1e-6
+# one extra count planted in one cell -> (histogram form it forces, count storage it forces on a u16-capable kernel)
+OVERFLOW_VARIANTS = {None: ("dense-capable", "u16"), 2048.0: ("lists", "u16"), 65535.0: ("lists", "u16"),
+                     65536.0: ("lists", "f32"), 7.5: ("lists", "f32"), 100000.5: ("lists", "f32")}
+
+
+def boundary_plan(Ng=200):
+    """{matrix: {gene: largest count}} of the planted genes (gene blocks of 64, quarters of 16 genes), the same genes in S and U.
+    Every boundary level is the largest count of a QUARTER of its own (the quarter blocks run to their quarter's largest count):
+      block 0: 2047 (gene 0, quarter 0; gene 7 beside it all zero), 257 (gene 16), 256 (gene 32), 255 (gene 48);
+      block 1: quarter 0 (genes 64..79) all zero, 700 (gene 85), 641 (gene 96), 640 (gene 112);
+      block 2: all zero (genes 128..191);  block 3, the ragged last block (Ng = 200): 639 (gene Ng - 3)."""
+    S = {0: 2047, 16: 257, 32: 256, 48: 255, 85: 700, 96: 641, 112: 640, Ng - 3: 639}
+    zero = [7] + list(range(64, 80)) + list(range(128, 192))
+    return {"S": S, "U": dict(S)}, zero
+
+
+def plant_boundary_counts(M, plan, zero, seed, top=80, split_ranks=True):
+    """M: (Ng, Nc) float32 counts, changed in place.  Gene g of `plan` gets its largest count K on `top` cells of the FIRST half
+    of the cells, counts uniform in [0, K) on the rest of that half and below min(K, 200) on the second half -- so that with the
+    cells split in two shards only the first shard's table goes past 256 levels in that block.  Genes in `zero` are all zero."""
+    g = torch.Generator().manual_seed(seed)
+    Nc = M.shape[1]
+    h = Nc // 2
+    for gene, K in plan.items():
+        row = torch.empty(Nc)
+        row[:h] = torch.floor(torch.rand(h, generator=g) * K)
+        row[h:] = torch.floor(torch.rand(Nc - h, generator=g) * (min(K, 200) if split_ranks else K))
+        row[torch.randperm(h, generator=g)[:top]] = float(K)
+        M[gene] = row
+    for gene in zero:
+        M[gene] = 0.0
+    return M
+
+
+def boundary_spec(kind="phase", noisemodel="NegativeBinomial", Nc=200, Ng=200, overflow=None, overflow_cell=None, seed=3):
+    """A small problem (Nc cells x Ng genes, four gene blocks) with the genes of boundary_plan planted in S (and U).
+    kind: "phase" | "vjoint" | "vjoint_lrmn" | "vcond" (make_velocity_spec's modes).  `overflow`: one extra count (a key of
+    OVERFLOW_VARIANTS) written into gene 20, cell `overflow_cell` (default: the last cell) of S -- and of U -- which forces the
+    lists form, and float32 storage where it is > 65535 or not an integer.  The prior of every planted gene is re-centred on its
+    data like the workloads centre theirs (log of the mean, half the std of log(S + 1))."""
+    from velocycle_amd.workloads import make_phase_spec, make_velocity_spec
+    if kind == "phase":
+        spec = make_phase_spec(Nc, Ng, seed=seed, noisemodel=noisemodel)
+    else:
+        spec = make_velocity_spec(Nc, Ng, kind, 1, 1, seed=seed, noisemodel=noisemodel)
+    plan, zero = boundary_plan(Ng)
+    S = plant_boundary_counts(spec.S.contiguous().clone(), plan["S"], zero, seed + 100)
+    mats = {"S": S}
+    if spec.kind == "velocity":
+        mats["U"] = plant_boundary_counts(spec.U.contiguous().clone(), plan["U"], zero, seed + 200)
+    if overflow is not None:
+        c = Nc - 1 if overflow_cell is None else overflow_cell
+        for M in mats.values():
+            M[20, c] = float(overflow)
+    spec.S = mats["S"]
+    if "U" in mats:
+        spec.U = mats["U"]
+    mu, sd = spec.mu_nu.clone(), spec.sd_nu.clone()
+    for gene in set(plan["S"]) | set(zero):
+        mu[gene, 0] = torch.log(S[gene].mean().clamp_min(1e-3))
+        sd[gene, 0] = (torch.log(S[gene] + 1).std() / 2).clamp_min(0.05)
+        mu[gene, 1:], sd[gene, 1:] = 0.0, 0.05     # (a flat gene: no cell of it on the relu kink of ElogU at the initial parameters)
+    spec.mu_nu, spec.sd_nu = mu, sd
+    if spec.kind == "velocity":
+        # unspliced counts as large as the spliced ones: E[U] = E[S] at the initial parameters (log beta = 0, gamma = 1, omega = 0)
+        mb = spec.mu_beta.clone()
+        mb[list(plan["U"])] = 0.0
+        spec.mu_beta = mb
+    if "ν" in spec.condition_on:
+        nu = spec.condition_on["ν"].clone()
+        nu[:, 0] = mu[:, 0]
+        spec.condition_on["ν"] = nu
+    spec.truth = None
+    return spec
+
+
+def nb_shape_inv_terms(spec, par, eps):
+    """Float64, on the host, per gene of a negative binomial problem at parameters `par` and draws `eps` (oracle site values):
+    r = 1 / shape_inv, and the pieces of d(-ELBO) / d shape_inv_locs (the chain rule of vc_si_grad: d/d log si = -r dL/dr ... ):
+      scale[g]  = r * (sum_j C_j / (r + j) + n_mat Nc |log r + 1| + sum_c |log(r + mu_c)| + (r + k_c) / (r + mu_c)) + |prior|
+                  -- the gene's sum of absolute terms, the yardstick of its shape_inv_locs gradient;
+      tables[m] = {gene: C (float64 array, C[j] = cells with count > j)} of the integer-count genes of matrix m."""
+    import math
+    p64 = problem_from_spec(spec, torch.float64)
+    par64 = {k: v.detach().cpu().double() for k, v in par.items()}
+    _, _, val, det = orc.loss_and_grads(p64, par64, {k: v.double() for k, v in eps.items() if not k.startswith("_")})
+    si = val["shape_inv"].double().numpy().reshape(-1)
+    r = 1.0 / si
+    mats = [(p64.S.numpy(), det["ElogS"].numpy())]
+    if spec.kind == "velocity":
+        mats.append((p64.U.numpy(), det["ElogU"].numpy()))
+    scale = np.zeros(spec.Ng)
+    tables = []
+    for M, Elog in mats:
+        mu = np.exp(Elog)
+        t = {}
+        for g in range(spec.Ng):
+            k = M[g]
+            per_cell = np.abs(np.log(r[g] + mu[g])) + (r[g] + k) / (r[g] + mu[g])
+            kmax = int(k.max()) if k.size else 0
+            hist = 0.0
+            if np.all(k == np.floor(k)) and kmax < (1 << 17):
+                C = (k[None, :] > np.arange(kmax)[:, None]).sum(1).astype(np.float64)
+                t[g] = C
+                hist = float((C / (r[g] + np.arange(kmax))).sum())
+            else:
+                from scipy.special import digamma
+                hist = float(np.abs(digamma(r[g] + k) - digamma(r[g])).sum())
+            scale[g] += r[g] * (hist + spec.Nc * abs(math.log(r[g]) + 1.0) + per_cell.sum())
+        tables.append(t)
+    scale += np.abs((spec.gamma_alpha - 1.0) - spec.gamma_beta * si)
+    return r, scale, tables

@@ -209,7 +209,106 @@ static void condition_cases() {
   }
 }
 
+// Dense tail-count tables (vc_build_dense_hist) and their per-quarter largest counts (vc_hist_quarter_rows) against a brute-force
+// recount, at the level limits of the device evaluators (255 / 256 / 257: the first 256 levels are prefetched; 639 / 640 / 641: the
+// second loop; 2047: the last dense bin).  kmax[g] = the largest count of gene g (0: an all-zero gene); `top` cells sit at it.
+static void dense_hist_case(const std::vector<int>& kmax, int Nc, int top, unsigned seed) {
+  std::mt19937 rng(seed);
+  const int Ng = (int)kmax.size(), Ng_pad = (Ng + 63) / 64 * 64, nblk = Ng_pad / 64;
+  std::vector<int> M((size_t)Ng * Nc, 0);
+  std::vector<unsigned> tab((size_t)Ng * VC_HIST_CAP, 0u);
+  for (int g = 0; g < Ng; ++g) {
+    const int K = kmax[(size_t)g];
+    CHECK(K >= 0 && K < VC_HIST_CAP && top <= Nc);
+    for (int c = 0; c < Nc && K > 0; ++c) {
+      int v = c < top ? K : (int)(rng() % (unsigned)K);             // below the top level: anything in [0, K)
+      if (c >= top && rng() % 3 == 0) v = 0;
+      M[(size_t)g * Nc + c] = v;
+      if (v) tab[(size_t)g * VC_HIST_CAP + v]++;
+    }
+  }
+  std::vector<float> HC;
+  std::vector<int> off, rows;
+  vc_build_dense_hist(tab.data(), Ng, Ng_pad, HC, off, rows);
+  CHECK((int)off.size() == nblk && (int)rows.size() == nblk);
+  size_t nrows = 0;
+  for (int gb = 0; gb < nblk; ++gb) {
+    int want = 0;
+    for (int g = gb * 64; g < std::min(Ng, gb * 64 + 64); ++g) want = std::max(want, kmax[(size_t)g]);
+    CHECK(rows[(size_t)gb] == want);
+    CHECK(off[(size_t)gb] == (int)nrows);
+    nrows += (size_t)rows[(size_t)gb];
+  }
+  CHECK(HC.size() == nrows * 64);
+  const double rs[] = {1e-4, 1e-2, 0.37, 1.0, 8.0, 123.4, 1e4};
+  for (int gb = 0; gb < nblk; ++gb)
+    for (int l = 0; l < 64; ++l) {
+      const int g = gb * 64 + l;
+      for (int j = 0; j < rows[(size_t)gb]; ++j) {
+        unsigned want = 0;                                           // C_j = cells whose count is > j
+        for (int c = 0; c < Nc && g < Ng; ++c) want += M[(size_t)g * Nc + c] > j;
+        CHECK(HC[((size_t)off[(size_t)gb] + j) * 64 + l] == (float)want);
+      }
+      if (g >= Ng) continue;
+      // sum_j C_j log(r + j) = sum_k cnt_k (lgamma(r + k) - lgamma(r)), and the digamma twin sum_j C_j / (r + j), in double
+      for (double r : rs) {
+        double tl = 0, ll = 0, ts = 0;
+        for (int j = 0; j < rows[(size_t)gb]; ++j) {
+          const double cj = HC[((size_t)off[(size_t)gb] + j) * 64 + l];
+          tl += cj * std::log(r + j);
+          ts += std::fabs(cj * std::log(r + j));
+        }
+        for (int k = 1; k < VC_HIST_CAP; ++k)
+          if (tab[(size_t)g * VC_HIST_CAP + k]) ll += (double)tab[(size_t)g * VC_HIST_CAP + k] * (std::lgamma(r + k) - std::lgamma(r));
+        CHECK(std::fabs(tl - ll) <= 1e-11 * (1.0 + ts));
+      }
+    }
+  // the quarter blocks: each quarter to its own genes' largest count; the blocks past 256 levels are split
+  std::vector<int> rows_q, split;
+  vc_hist_quarter_rows(HC, off, rows, 256, rows_q, split);
+  CHECK(rows_q.size() == rows.size() * 4);
+  std::vector<int> want_split;
+  for (int gb = 0; gb < nblk; ++gb) {
+    int mx = 0;
+    for (int qd = 0; qd < 4; ++qd) {
+      int want = 0;
+      for (int g = gb * 64 + 16 * qd; g < std::min(Ng, gb * 64 + 16 * qd + 16); ++g) want = std::max(want, kmax[(size_t)g]);
+      CHECK(rows_q[(size_t)gb * 4 + qd] == want);
+      mx = std::max(mx, want);
+    }
+    CHECK(mx == rows[(size_t)gb]);
+    if (rows[(size_t)gb] > 256) want_split.push_back(gb);
+  }
+  CHECK(split == want_split);
+}
+
+static void dense_hist_cases() {
+  const int lv[] = {0, 1, 255, 256, 257, 639, 640, 641, 2047};
+  // one largest count per block (all 64 genes at it, or one gene at it beside small genes), Ng not a multiple of 64
+  for (int K : lv) {
+    dense_hist_case(std::vector<int>(64, K), 24, 20, 10 + K);
+    std::vector<int> km(100, K > 0 ? std::min(K, 3) : 0);
+    km[37] = K;
+    km[99] = K;                                                      // the last gene of a ragged block
+    dense_hist_case(km, 30, 20, 20 + K);
+  }
+  // 200 genes: every level limit in block 0, an all-zero gene, one all-zero quarter next to a quarter past 640 levels in block 1,
+  // block 2 entirely zero, a ragged block 3
+  std::vector<int> km(200, 0);
+  for (int i = 0; i < 9; ++i) km[(size_t)i] = lv[i];
+  for (int g = 9; g < 64; ++g) km[(size_t)g] = 1 + g % 7;
+  for (int g = 64; g < 80; ++g) km[(size_t)g] = 0;                   // quarter 0 of block 1: zero
+  for (int g = 80; g < 96; ++g) km[(size_t)g] = 640 + (g & 3);        // quarter 1: 640 .. 643
+  for (int g = 96; g < 128; ++g) km[(size_t)g] = 5;
+  for (int g = 192; g < 200; ++g) km[(size_t)g] = g == 199 ? 2047 : 2;
+  dense_hist_case(km, 40, 20, 7);
+  dense_hist_case(std::vector<int>(1, 0), 5, 0, 8);                 // one all-zero gene
+  dense_hist_case(std::vector<int>(130, 0), 5, 0, 9);               // every block empty
+  dense_hist_case(std::vector<int>(1, 2047), 1, 1, 10);             // a single cell
+}
+
 int main() {
+  dense_hist_cases();
   condition_cases();
   {
     std::mt19937 rng(5);

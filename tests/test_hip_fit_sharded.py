@@ -30,14 +30,26 @@ def _tb(err):
 
 @pytest.mark.parametrize("mode", ["perf", "parity"])
 def test_sharded_fit_equals_single_process_fit(mode, tmp_path):
+    _sharded_vs_single(mode, tmp_path, [])
+
+
+def test_sharded_fit_with_a_count_only_one_shard_stores_as_float32(tmp_path):
+    """A count of 70 000 in rank 1's cells only: rank 1 keeps float32 counts, rank 0 narrows its own to uint16.  The count storage is
+    the same arithmetic on the same layout, so the ranks' Tuning / layout check passes and the run matches the single process."""
+    a, b = _sharded_vs_single("perf", tmp_path, ["--plant-overflow"])
+    assert str(a["phase_storage"]) == "f32" and str(a["vel_storage"]) == "f32"          # one process: the whole data set
+    assert str(b["phase_storage"]) == "u16" and str(b["vel_storage"]) == "u16"          # rank 0 of the sharded run (rank 1: f32)
+
+
+def _sharded_vs_single(mode, tmp_path, extra):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     one, two = str(tmp_path / "one.npz"), str(tmp_path / "two.npz")
-    r1 = subprocess.run([sys.executable, "tests/fit_shard_worker.py", one, mode], cwd=ROOT, env=env,
+    r1 = subprocess.run([sys.executable, "tests/fit_shard_worker.py", one, mode] + extra, cwd=ROOT, env=env,
                         capture_output=True, text=True, timeout=900)
     assert r1.returncode == 0, _tb(r1.stderr)
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                          "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-                         "tests/fit_shard_worker.py", two, mode],
+                         "tests/fit_shard_worker.py", two, mode] + extra,
                         cwd=ROOT, env=dict(env, VC_BENCH_ONE_DEVICE="1"), capture_output=True, text=True, timeout=900)
     assert r2.returncode == 0, _tb(r2.stderr)
     a, b = np.load(one), np.load(two)
@@ -54,7 +66,7 @@ def test_sharded_fit_equals_single_process_fit(mode, tmp_path):
         assert np.allclose(a[k][:8], b[k][:8], rtol=1e-6, atol=0), (k, np.abs(a[k][:8] / b[k][:8] - 1).max())
         assert np.allclose(a[k], b[k], rtol=5e-3, atol=0), (k, np.abs(a[k] / b[k] - 1).max())
     for k in a.files:
-        if k in ("world", "nc_local", "vel_kernel", "phase_losses", "vel_losses"):
+        if k in ("world", "nc_local", "vel_kernel", "phase_losses", "vel_losses", "phase_storage", "vel_storage"):
             continue
         assert a[k].shape == b[k].shape, (k, a[k].shape, b[k].shape)
         fin = np.isfinite(a[k])
@@ -67,3 +79,4 @@ def test_sharded_fit_equals_single_process_fit(mode, tmp_path):
             assert np.abs(x - y).max() <= 0.25 * scale, (k, np.abs(x - y).max(), scale)
     # the gathered per-cell results really cover every cell of both samples
     assert a["vel_post_ω"].shape[-1] == 3002 and b["phase_phis_pyro"].shape == (2, 3002)
+    return a, b

@@ -1332,17 +1332,9 @@ static int fin_histograms(vc_engine* e, FinalizeState& s) {
     hc.resize(hc.size() + 64, 0.f);          // (a row of padding: the prefetch of an empty block reads row 0)
     // gene blocks that hold a highly expressed gene: the one-launch tail gives each of them four quarter blocks (16 genes, one wave per
     // SIMD of a CU of their own: vc_common.h, vc_hist_dense16_finish<true>), every quarter to ITS genes' largest count
-    std::vector<int> hc_rows_q(hc_rows.size() * 4, 0), hc_split;
-    for (size_t i = 0; i < hc_rows.size(); ++i) {
-      for (int qd = 0; qd < 4; ++qd) {
-        int rq = 0;
-        for (int j = hc_rows[i] - 1; j >= 0 && !rq; --j)
-          for (int l = 16 * qd; l < 16 * qd + 16; ++l)
-            if (hc[((size_t)hc_off[i] + j) * 64 + l] != 0.f) { rq = j + 1; break; }
-        hc_rows_q[i * 4 + qd] = rq;
-      }
-      if (hc_rows[i] > VC_HIST_SPLIT_ROWS) hc_split.push_back((int)i);
-    }
+    // (vc_host_logic.h: vc_hist_quarter_rows)
+    std::vector<int> hc_rows_q, hc_split;
+    vc_hist_quarter_rows(hc, hc_off, hc_rows, VC_HIST_SPLIT_ROWS, hc_rows_q, hc_split);
     b.n_hc_split = (int)hc_split.size();
     if (hc_split.empty()) hc_split.push_back(0);
     TRY(upload(e, hc, &b.HC));

@@ -149,6 +149,26 @@ static inline void vc_build_dense_hist(const unsigned* tab, int Ng, int Ng_pad, 
   }
 }
 
+// Per-quarter largest counts of the dense tables (the quarter blocks of vc_common.h: vc_hist_dense16_finish<true>): for every table
+// block i (matrix * nblk + gene block) and quarter qd (genes 16 qd .. 16 qd + 15 of the block), rows_q[i * 4 + qd] = 1 + the highest
+// row j < rows[i] at which one of the quarter's genes has a non-zero C_j (0: all zero); split = the blocks with rows[i] > split_rows,
+// which the one-launch tail gives four quarter blocks.  HC holds rows of 64 floats, block i starting at row off[i].
+static inline void vc_hist_quarter_rows(const std::vector<float>& HC, const std::vector<int>& off, const std::vector<int>& rows,
+                                        int split_rows, std::vector<int>& rows_q, std::vector<int>& split) {
+  rows_q.assign(rows.size() * 4, 0);
+  split.clear();
+  for (size_t i = 0; i < rows.size(); ++i) {
+    for (int qd = 0; qd < 4; ++qd) {
+      int rq = 0;
+      for (int j = rows[i] - 1; j >= 0 && !rq; --j)
+        for (int l = 16 * qd; l < 16 * qd + 16; ++l)
+          if (HC[((size_t)off[i] + j) * 64 + l] != 0.f) { rq = j + 1; break; }
+      rows_q[i * 4 + qd] = rq;
+    }
+    if (rows[i] > split_rows) split.push_back((int)i);
+  }
+}
+
 // Tasks of the histogram kernel: runs of <= 64 histogram entries of one gene and matrix {gene, matrix, begin, end},
 // sorted by gene; tptr[g] = first task of gene g.  ptr is the CSR of [S genes..., U genes..., end].
 static inline void vc_build_hist_tasks(const std::vector<int>& ptr, int Ng, std::vector<int>& task, std::vector<int>& tptr) {

@@ -12,6 +12,7 @@ at step 0 with identical hyper-parameters, so a single flat state is equivalent.
 from __future__ import annotations
 
 import math
+import re
 from typing import Dict, List, Optional
 
 import torch
@@ -239,6 +240,11 @@ class FlatClippedAdam:
             self.t_dev.fill_(float(self.t))
 
 
+def kernel_layout_name(name: str) -> str:
+    """The likelihood kernel's name without its count storage tag (`,u16`): what the ranks of a sharded run have to agree on."""
+    return re.sub(r",u16(?=[,>])", "", name)
+
+
 class SVIRunner:
     """mode="parity": eps drawn on the host in the reference's RNG order (seed-for-seed comparable
     with the reference), loss read back every step.  mode="perf": eps from the in-kernel Philox
@@ -399,8 +405,11 @@ class SVIRunner:
             xsize = e.exchange_size()
         except Exception:
             xsize = -1
-        # the whole kernel name (one-hot batch detection changes its NB argument, not only genes per lane) and the batch count
-        desc = repr((self.tuning.digest(), e.header, e.n_global, stats.get("main_kernel", ""), stats.get("onehot_batches", 0), xsize))
+        # the whole kernel name (one-hot batch detection changes its NB argument, not only genes per lane) and the batch count --
+        # but not its count storage tag: uint16 storage is chosen per rank from that rank's own counts (every one an integer
+        # <= 65535), is the same arithmetic as float32, and changes neither the layout nor the exchange
+        desc = repr((self.tuning.digest(), e.header, e.n_global, kernel_layout_name(stats.get("main_kernel", "")),
+                     stats.get("onehot_batches", 0), xsize))
         h = int.from_bytes(hashlib.sha256(desc.encode()).digest()[:8], "little") >> 2
         dev = e.device if dist.get_backend(self.pg) == "nccl" else "cpu"
         lo = torch.tensor([h], dtype=torch.int64, device=dev)
