@@ -13,8 +13,8 @@
 //                omega_c(t + 1) into the cell records of its 256 cells; block 0 also assembles the loss of step t
 //                (fp64, fixed order); extra blocks evaluate the negative-binomial histogram terms for shape_inv(t + 1).
 //
-// The arithmetic of every piece is the one of vc_small_kernels.hip (K_pre / K_post / K_fin / ClippedAdam), statement by
-// statement; tests/test_hip_fused.py holds the two paths against each other.  eps comes from the Philox stream only
+// The arithmetic of every piece is the one of vc_small_kernels.hip (K_pre / K_post / K_fin / ClippedAdam): the per-site
+// functions of vc_site_math.h and vc_common.h, shared by both; tests/test_hip_fused.py holds the two paths against each other.  eps comes from the Philox stream only
 // (seed, step, index): the host-eps parity path stays on the unfused kernels.  No Philox draw sits on the critical path:
 // extra blocks of K_omega(t) draw the whole eps vector of step t + 2 into a three-slot ring (EPS[step % 3]) while the few
 // blocks of the nu_omega chain run; K_tail / K_omega read the draws of the step being finished (for the scale gradients)
@@ -27,9 +27,8 @@
 #pragma clang fp contract(off)
 #include "vc_common.h"
 #include "vc_tail_spec.h"
+#include "vc_site_math.h"
 
-#define VC_PG_WAVES 16
-#define VC_MAXQ (2 * VC_MAXH + 1 + VC_MAXNB + 3)
 #define VC_MAXOWN 5      // parameters one (gene, role) thread owns (the LRMN cov_factor row is split over two roles)
 #define VC_COVW 4        // cov_factor entries per role: role 14 holds k = 0..3, role 15 k = 4..7
 
@@ -323,20 +322,16 @@ __device__ __forceinline__ void vc_tail_gene_block(const VcDims& d, const VcBufs
       for (int w = 0; w < VC_PG_WAVES; ++w) t += sm[w][q][lane];
       return t;
     };
-    // ---- chain rule to the gradients of the owned parameters (statement by statement vc_post_gene_block) -------
+    // ---- chain rule to the gradients of the owned parameters (vc_site_math.h, as vc_post_gene_block) -------------
     if (live) {
       if (r_nu) {
         if (!CND(VC_SITE_NU)) {
-          const float x = in[0], sd = in[1];
-          const float gx = T(role) - rw * (x - in[2]) / (sd * sd);
+          const float gx = vc_prior_grad(T(role), in[0], in[2], in[1], rw);
           gg[0] = -gx;
-          gg[1] = -gx * expf(pp[1]) * in[3] - rw;
+          gg[1] = vc_mf_uscale_grad(gx, pp[1], in[3], rw);
         }
       } else if (r_dnu) {
-        if (!CND(VC_SITE_DNU)) {
-          const float x = in[0], sd = in[1];
-          gg[0] = -(T(role) - rw * x / (sd * sd));
-        }
+        if (!CND(VC_SITE_DNU)) gg[0] = -vc_prior_grad(T(role), in[0], 0.f, in[1], rw);
       } else if (r_si) {
         const float r = in[0];
         const float U_r = (d.kind == VC_KIND_PHASE) ? T(K) : (d.kind == VC_KIND_VFULL ? T(K + 2) : 0.f);
@@ -347,53 +342,32 @@ __device__ __forceinline__ void vc_tail_gene_block(const VcDims& d, const VcBufs
       } else if (r_mf || r_core || r_cov) {
         const float gam = in[0];
         float U_lb, U_lg;
-        if (d.kind == VC_KIND_VFULL) { U_lb = -T(K); U_lg = T(K + 1) * gam; }
-        else { U_lb = -T(0); U_lg = T(1) * gam; }
+        vc_lb_lg_lik(d.kind, K, gam, T, U_lb, U_lg);
         float g_lg = 0.f, g_lb = 0.f;
-        if (!CND(VC_SITE_LOGGAMMA)) g_lg = U_lg - rw * (in[1] - in[3]) / (in[2] * in[2]);
-        if (!CND(VC_SITE_LOGBETA)) g_lb = U_lb - rw * (in[4] - in[6]) / (in[5] * in[5]);
+        if (!CND(VC_SITE_LOGGAMMA)) g_lg = vc_prior_grad(U_lg, in[1], in[3], in[2], rw);
+        if (!CND(VC_SITE_LOGBETA)) g_lb = vc_prior_grad(U_lb, in[4], in[6], in[5], rw);
         if (r_mf) {
           if (role == 13) {
             const bool cg = CND(VC_SITE_LOGGAMMA);
             gg[0] = -g_lg;
-            gg[1] = cg ? 0.f : -g_lg * expf(pp[1]) * in[7] - rw;
+            gg[1] = cg ? 0.f : vc_mf_uscale_grad(g_lg, pp[1], in[7], rw);
           } else {
             const bool cb = CND(VC_SITE_LOGBETA);
             gg[0] = -g_lb;
-            gg[1] = cb ? 0.f : -g_lb * expf(pp[1]) * in[7] - rw;
+            gg[1] = cb ? 0.f : vc_mf_uscale_grad(g_lb, pp[1], in[7], rw);
           }
         } else {
-          const bool cb = CND(VC_SITE_LOGBETA);
-          const float A = g_lb;
-          const float ent = cb ? 0.f : rw;
           const float delta = in[7], sgam = in[8];
-          const float sb = expf(r_core ? pp[1] : in[9]);
           const float rho_real = r_core ? pp[2] : in[10];
-          const float sg = sigmoidf_(rho_real / d.rho_scale);
-          const float rho = sg * 1.998f - 0.999f;
-          const float om = 1.f - rho * rho, sq = sqrtf(om);
-          const float dl_ddelta = -g_lg - A * rho * sb / sgam;
-          const float dl_dsg = A * rho * sb * delta / (sgam * sgam);
+          const VcLrmnChain ch = vc_lrmn_chain(d, g_lg, g_lb, delta, sgam, r_core ? pp[1] : in[9], rho_real);
           if (r_core) {
-            const float eb = in[9];
-            gg[0] = -A;
-            gg[1] = -A * (rho * delta / sgam + sq * eb) * sb - ent;
-            float g_rho = -A * (sb * delta / sgam - sb * rho * eb / sq) + ent * rho / om;
-            float g_rr = g_rho * 1.998f * sg * (1.f - sg) / d.rho_scale;
-            if (!CND(VC_SITE_RHO_REAL)) g_rr += rw * (rho_real - d.rho_mean) / (d.rho_std * d.rho_std);
-            gg[2] = g_rr;
-            gg[3] = -g_lg;
-            const float dg = expf(pp[4]);
-            const float ed = in[10];
-            gg[4] = (dl_ddelta * ed / (2.f * sqrtf(dg)) + dl_dsg / (2.f * sgam)) * dg;
+            const VcLrmnCoreGrad cg = vc_lrmn_core_grad(d, ch, g_lg, g_lb, CND(VC_SITE_LOGBETA), CND(VC_SITE_RHO_REAL), delta, sgam,
+                                                        rho_real, in[9], pp[4], in[10], rw);
+            gg[0] = cg.loc_b; gg[1] = cg.uscale_b; gg[2] = cg.rho_real; gg[3] = cg.loc; gg[4] = cg.udiag;
           } else {
 #pragma unroll
             for (int k = 0; k < VC_COVW; ++k)
-              if (k < nown) {
-                const float w = expf(pp[k]);
-                const float ew = kbase ? ew_old[VC_COVW + k] : ew_old[k];
-                gg[k] = (w > 0.f) ? (dl_ddelta * ew + dl_dsg * w / sgam) * w : 0.f;
-              }
+              if (k < nown) gg[k] = vc_lrmn_cov_grad(ch, sgam, pp[k], kbase ? ew_old[VC_COVW + k] : ew_old[k]);
           }
         }
       }
@@ -439,7 +413,7 @@ __device__ __forceinline__ void vc_tail_gene_block(const VcDims& d, const VcBufs
           } else {
             lik = (dnu_pre_on && first) ? vc_dnu_range_finish(d, b, g, dnu_pre) : vc_dnu_range_sum(d, b, g, q);
           }
-          gq = -(lik - rw * (first ? dq_lat : b.lat[VC_SITE_DNU][jq]) / (sd * sd));
+          gq = -vc_prior_grad(lik, first ? dq_lat : b.lat[VC_SITE_DNU][jq], 0.f, sd, rw);
         }
         if (phase == VC_PH_A) vc_xput(xb, po, gq);
         else {
@@ -473,7 +447,7 @@ __device__ __forceinline__ void vc_tail_gene_block(const VcDims& d, const VcBufs
   if (!samp) return;                    // phase A ends here (uniform per launch: no barrier is skipped by part of a block)
 
   VC_WSTAMP(0, 4);
-  // ---- the guide sample of step s from the fresh parameters (statement by statement vc_pre_kernel) ---------------
+  // ---- the guide sample of step s from the fresh parameters (vc_site_math.h, as vc_pre_kernel) -------------------
   float logp = logp_dnu, logq = 0.f;
   double lpr = 0.0;
   if (g < d.Ng_pad && !live) {
@@ -490,9 +464,9 @@ __device__ __forceinline__ void vc_tail_gene_block(const VcDims& d, const VcBufs
       float x;
       if (CND(VC_SITE_NU)) x = b.cnd[VC_SITE_NU][jj];
       else {
-        const float u = pp[1];
-        x = pp[0] + expf(u) * e;
-        logq += -0.5f * e * e - u - 0.5f * VC_LOG_2PI;
+        float lq;
+        x = vc_mf_draw(pp[0], pp[1], e, lq);
+        logq += lq;
       }
       logp += vc_normal_lp(x, in[2], in[1]);
       b.lat[VC_SITE_NU][jj] = x;
@@ -504,7 +478,7 @@ __device__ __forceinline__ void vc_tail_gene_block(const VcDims& d, const VcBufs
       GT[role * NP] = x;
     } else if (r_si) {
       const float si = CND(VC_SITE_SHAPE_INV) ? b.cnd[VC_SITE_SHAPE_INV][g] : expf(pp[0]);
-      logp += d.gamma_alpha * logf(d.gamma_beta) + (d.gamma_alpha - 1.f) * logf(si) - d.gamma_beta * si - d.lgamma_alpha;
+      logp += vc_gamma_lp(d, si);
       b.lat[VC_SITE_SHAPE_INV][g] = si;
       const float r = 1.0f / si;
       GT[(KT + 2) * NP] = r;
@@ -517,19 +491,17 @@ __device__ __forceinline__ void vc_tail_gene_block(const VcDims& d, const VcBufs
     } else if (role == 12 && boot && !nb) {
       GT[(KT + 2) * NP] = 1.0f;
     } else if (r_mf && role == 13) {
-      const float eg = e0;
-      const float ug = pp[1];
-      const float lg_guide = pp[0] + expf(ug) * eg;
-      if (!CND(VC_SITE_LOGGAMMA)) logq += -0.5f * eg * eg - ug - 0.5f * VC_LOG_2PI;
+      float lq;
+      const float lg_guide = vc_mf_draw(pp[0], pp[1], e0, lq);
+      if (!CND(VC_SITE_LOGGAMMA)) logq += lq;
       const float lg = CND(VC_SITE_LOGGAMMA) ? b.cnd[VC_SITE_LOGGAMMA][g] : lg_guide;
       logp += vc_normal_lp(lg, in[3], in[2]);
       b.lat[VC_SITE_LOGGAMMA][g] = lg;
       GT[(KT + 1) * NP] = expf(lg);
     } else if (r_mf) {
-      const float eb = e0;
-      const float ub = pp[1];
-      const float lb_guide = pp[0] + expf(ub) * eb;
-      if (!CND(VC_SITE_LOGBETA)) logq += -0.5f * eb * eb - ub - 0.5f * VC_LOG_2PI;
+      float lq;
+      const float lb_guide = vc_mf_draw(pp[0], pp[1], e0, lq);
+      if (!CND(VC_SITE_LOGBETA)) logq += lq;
       const float lbv = CND(VC_SITE_LOGBETA) ? b.cnd[VC_SITE_LOGBETA][g] : lb_guide;
       logp += vc_normal_lp(lbv, in[6], in[5]);
       b.lat[VC_SITE_LOGBETA][g] = lbv;
@@ -557,24 +529,15 @@ __device__ __forceinline__ void vc_tail_gene_block(const VcDims& d, const VcBufs
     float delta = sm_ws[0][lane][0];
     float w2 = sm_ws[0][lane][1];
     if (d.R > VC_COVW) { delta += sm_ws[1][lane][0]; w2 += sm_ws[1][lane][1]; }
-    const float dg = expf(pp[4]);
-    delta += sqrtf(dg) * ed;
-    const float sgam = sqrtf(w2 + dg);
-    const float lg_guide = pp[3] + delta;
-    const float rho_real_g = pp[2];
-    const float rho = sigmoidf_(rho_real_g / d.rho_scale) * 1.998f - 0.999f;
-    const float ub = pp[1];
-    const float sb = expf(ub);
-    const float tt = sb * sqrtf(1.f - rho * rho);
-    const float lb_guide = pp[0] + rho * sb * delta / sgam + tt * eb;
-    if (!CND(VC_SITE_LOGBETA)) logq += -0.5f * eb * eb - logf(tt) - 0.5f * VC_LOG_2PI;
-    b.lat_delta[g] = delta;
-    b.lat_sgam[g] = sgam;
-    const float rho_val = CND(VC_SITE_RHO_REAL) ? b.cnd[VC_SITE_RHO_REAL][g] : rho_real_g;
+    const VcLrmnDraw q = vc_lrmn_draw(d, delta, w2, pp[4], ed, pp[3], pp[0], pp[1], pp[2], eb);
+    if (!CND(VC_SITE_LOGBETA)) logq += q.lq;
+    b.lat_delta[g] = q.delta;
+    b.lat_sgam[g] = q.sgam;
+    const float rho_val = CND(VC_SITE_RHO_REAL) ? b.cnd[VC_SITE_RHO_REAL][g] : pp[2];
     logp += vc_normal_lp(rho_val, d.rho_mean, d.rho_std);
     b.lat[VC_SITE_RHO_REAL][g] = rho_val;
-    const float lg = CND(VC_SITE_LOGGAMMA) ? b.cnd[VC_SITE_LOGGAMMA][g] : lg_guide;
-    const float lbv = CND(VC_SITE_LOGBETA) ? b.cnd[VC_SITE_LOGBETA][g] : lb_guide;
+    const float lg = CND(VC_SITE_LOGGAMMA) ? b.cnd[VC_SITE_LOGGAMMA][g] : q.lg;
+    const float lbv = CND(VC_SITE_LOGBETA) ? b.cnd[VC_SITE_LOGBETA][g] : q.lb;
     logp += vc_normal_lp(lg, in[3], in[2]) + vc_normal_lp(lbv, in[6], in[5]);
     b.lat[VC_SITE_LOGGAMMA][g] = lg;
     b.lat[VC_SITE_LOGBETA][g] = lbv;
@@ -727,12 +690,8 @@ __device__ __forceinline__ void vc_tail_cell_block(const VcDims& d, const VcBufs
           }
       }
       if (!cxy) {
-        float dphi = A[0];
-        if (d.kind == VC_KIND_VFULL) dphi += om * A[1] + A[2] * dom;
-        const float x = xy.x, y = xy.y;
-        const float inv = 1.0f / (x * x + y * y);
-        const float gx = -(dphi * (-y * inv) - (x - pxy.x));
-        const float gy = -(dphi * (x * inv) - (y - pxy.y));
+        const float2 gxy = vc_phixy_grad(d.kind, A, om, dom, xy.x, xy.y, pxy.x, pxy.y);
+        const float gx = gxy.x, gy = gxy.y;
         *reinterpret_cast<float2*>(G + poff) = make_float2(gx, gy);
         pp.x = vc_adam_elem(pp.x, gx, pm.x, pv.x, o.step_size, o.b1, o.b2, o.eps, o.clip, o.c2, vc_wd_at(o.wd, o.frozen, poff));
         pp.y = vc_adam_elem(pp.y, gy, pm.y, pv.y, o.step_size, o.b1, o.b2, o.eps, o.clip, o.c2, vc_wd_at(o.wd, o.frozen, poff));
@@ -752,13 +711,8 @@ __device__ __forceinline__ void vc_tail_cell_block(const VcDims& d, const VcBufs
     // partial sums of d loglik / d nu_omega[x,h] = sum_c A3_c D[x,c] zeta_omega_h(phi_c) at the phases of step s - 1
     // (their sin / cos are in the cell record; higher harmonics by the angle-addition recurrence, as K_pre built them)
     const float a3 = in_range ? (d.kind == VC_KIND_VFULL ? A[2] : A[0]) : 0.f;
-    const float s1 = sc_old.x, c1 = sc_old.y;
     float sk[VC_MAXH], ck[VC_MAXH];
-    sk[0] = s1; ck[0] = c1;
-    for (int k = 1; k < d.Hw && k < VC_MAXH; ++k) {
-      sk[k] = sk[k - 1] * c1 + ck[k - 1] * s1;
-      ck[k] = ck[k - 1] * c1 - sk[k - 1] * s1;
-    }
+    vc_harmonics(sc_old.x, sc_old.y, d.Hw, sk, ck);
     for (int xq = 0; xq < d.Nx; ++xq) {
       const float dx = in_range ? (xq < 2 ? dx01[xq] : b.Dm[(size_t)xq * d.Nc + c]) : 0.f;
       for (int h = 0; h < d.Nhw; ++h) {
@@ -802,24 +756,18 @@ __device__ __forceinline__ void vc_tail_cell_block(const VcDims& d, const VcBufs
     float x, y;
     if (cxy) {
       x = b.cnd[VC_SITE_PHIXY][2 * c]; y = b.cnd[VC_SITE_PHIXY][2 * c + 1];
-      loss += 0.5 * ((double)(x - px) * (x - px) + (double)(y - py) * (y - py)) + (double)VC_LOG_2PI;
     } else {
       x = pp.x + ex;
       y = pp.y + ey;
-      loss += 0.5 * ((double)(x - px) * (x - px) + (double)(y - py) * (y - py)) - 0.5 * ((double)ex * ex + (double)ey * ey);
     }
+    loss += vc_phixy_loss(x, y, px, py, ex, ey, cxy);
     if (!cxy || boot) {          // conditioned phases never change: their record is written once
       *reinterpret_cast<float2*>(b.lat[VC_SITE_PHIXY] + 2 * (size_t)c) = make_float2(x, y);
       const float ph = atan2f(y, x);          // (the deterministic site only)
       float s1, c1;
       vc_dir_sincos(x, y, &s1, &c1);
       float sk[VC_MAXH], ck[VC_MAXH];
-      sk[0] = s1; ck[0] = c1;
-      const int hm = d.H > d.Hw ? d.H : d.Hw;          // the W table (vc_put_w) goes up to Hw
-      for (int k = 1; k < hm && k < VC_MAXH; ++k) {
-        sk[k] = sk[k - 1] * c1 + ck[k - 1] * s1;
-        ck[k] = ck[k - 1] * c1 - sk[k - 1] * s1;
-      }
+      vc_harmonics(s1, c1, d.H > d.Hw ? d.H : d.Hw, sk, ck);          // the W table (vc_put_w) goes up to Hw
       s1_new = s1; c1_new = c1;
       float2* ct = reinterpret_cast<float2*>(b.CT + (size_t)cp * d.ctw);
       for (int k = 0; k < d.H; ++k) { ct[2 * k] = make_float2(sk[k], sk[k]); ct[2 * k + 1] = make_float2(ck[k], ck[k]); }
@@ -1387,26 +1335,10 @@ __device__ __forceinline__ void vc_nuw_params(const VcDims& d, const VcBufs& b, 
     float p = nws[tt];                         // the snapshot of this step: block 0 overwrites P / m / v below
     if (!boot) {
       float gx = 0.f;
-      if (!cnd) {
-        const float x = nws[3 * VC_NWE + j], sd = b.sd_w[j];
-        gx = sh.up[j] - rw * (x - b.mu_w[j]) / (sd * sd);
-      }
+      if (!cnd) gx = vc_prior_grad(sh.up[j], nws[3 * VC_NWE + j], b.mu_w[j], b.sd_w[j], rw);
       const long long ei = eps_index(j, ce);
       const float eo = ei >= 0 ? eps_old[ei] : 0.f;          // eps of the finished step for this element
-      float gv;
-      if (!lrmn) {
-        if (ce == 0) gv = -gx;
-        else gv = cnd ? 0.f : -gx * expf(p) * eo - rw;
-      } else {
-        if (ce == 0) gv = -gx;
-        else if (ce <= d.R) {
-          const float w = expf(p);
-          gv = (w > 0.f) ? -gx * eo * w : 0.f;
-        } else {
-          const float dg = expf(p);
-          gv = -gx * eo / (2.f * sqrtf(dg)) * dg;
-        }
-      }
+      const float gv = vc_nuw_elem_grad(lrmn, d.R, ce, gx, p, eo, cnd, rw);
       float mm = nws[VC_NWE + tt], vv = nws[2 * VC_NWE + tt];
       p = vc_adam_elem(p, gv, mm, vv, step_size, a.b1, a.b2, a.eps, a.clip, b.step_size[1], vc_wd_at(a.wd, a.frozen, off));
       if (first) {
@@ -1432,14 +1364,13 @@ __device__ __forceinline__ void vc_nuw_params(const VcDims& d, const VcBufs& b, 
     if (!lrmn) {
       const float e = en(1);
       const float u = np[1];
-      val = np[0] + expf(u) * e;
-      lq = -0.5f * e * e - u - 0.5f * VC_LOG_2PI;
+      val = vc_mf_draw(np[0], u, e, lq);
     } else {
       float delta = 0.f;
       for (int k = 0; k < d.R; ++k) delta += expf(np[1 + k]) * en(1 + k);
       const float ed = en(d.R + 1);
-      delta += sqrtf(expf(np[d.R + 1])) * ed;
-      val = np[0] + delta;
+      const float ud = np[d.R + 1];
+      val = vc_lrmn_row_draw(np[0], delta, ud, ed, delta);
       if (first) b.lat_delta[i] = delta;
     }
     const float x = cnd ? b.cnd[VC_SITE_NUOMEGA][j] : val;
@@ -1464,14 +1395,9 @@ __device__ __forceinline__ void vc_nuw_params(const VcDims& d, const VcBufs& b, 
 // (sin, cos of its phase of step s: s1, c1)
 __device__ __forceinline__ void vc_nuw_cells(const VcDims& d, const VcBufs& b, int c, float s1, float c1, const VcNuwShared& sh) {
   if (c < d.Nc) {
-    // harmonics by the angle-addition recurrence; fully unrolled (compile-time indices keep sk / ck in registers)
+    // all VC_MAXH harmonics: a compile-time count, fully unrolled (compile-time indices keep sk / ck in registers)
     float sk[VC_MAXH], ck[VC_MAXH];
-    sk[0] = s1; ck[0] = c1;
-#pragma unroll
-    for (int k = 1; k < VC_MAXH; ++k) {
-      sk[k] = sk[k - 1] * c1 + ck[k - 1] * s1;
-      ck[k] = ck[k - 1] * c1 - sk[k - 1] * s1;
-    }
+    vc_harmonics(s1, c1, VC_MAXH, sk, ck);
     float omega = 0.f, domega = 0.f;
     for (int xq = 0; xq < d.Nx; ++xq) {
       const float* nwp = sh.nuw + xq * d.Nhw;

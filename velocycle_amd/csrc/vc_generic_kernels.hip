@@ -4,7 +4,7 @@
 // velocity_inference_guide.py:91-92), more than 64 angular-speed coefficients.  Nothing here is a template over H / Nb / rank:
 // harmonics, batches and low-rank columns are loops, the per-gene state of the likelihood kernel lives in the LDS instead of
 // registers.  Slower than the fast set by design (the fast instantiations stay selected wherever they exist); the arithmetic is
-// the fast kernels' statement by statement, so both are held against the same float64 oracle at the same tolerances
+// the fast kernels' (the shared vc_site_math.h), so both are held against the same float64 oracle at the same tolerances
 // (tests/test_hip_sweep.py).  Only the unfused sequence exists here: K_pre -> K_main -> K_post -> K_fin -> ClippedAdam
 // (vc_elbo_grad + vc_clipped_adam; cells sharded: the all-reduce of the gradient buffer between them).
 //
@@ -16,6 +16,7 @@
 //   vc_fin_generic_kernel                 loss assembly + the nu_omega / LRMN tail gradients for any number of coefficients
 #pragma clang fp contract(off)
 #include "vc_main_math.h"        // v2f helpers, observation models
+#include "vc_site_math.h"
 
 // ---------------------------------------------------------------------------------------------
 // K_main, generic
@@ -266,9 +267,10 @@ __global__ __launch_bounds__(256) void vc_pre_generic_kernel(const VcDims d, con
           else {
             const float e = eps(d.eoff[VC_E_NU] + j, d.eoff[VC_E_NU] + j);
             const float u = P[d.poff[VC_P_NU_USCALES] + j];
-            const float xg = P[d.poff[VC_P_NU_LOCS] + j] + expf(u) * e;
+            float lq;
+            const float xg = vc_mf_draw(P[d.poff[VC_P_NU_LOCS] + j], u, e, lq);
             if (CND(VC_SITE_NU)) x = b.cnd[VC_SITE_NU][j];
-            else { x = xg; logq += -0.5f * e * e - u - 0.5f * VC_LOG_2PI; }
+            else { x = xg; logq += lq; }
             logp += vc_normal_lp(x, b.mu_nu[j], b.sd_nu[j]);
             b.lat[VC_SITE_NU][j] = x;
           }
@@ -291,7 +293,7 @@ __global__ __launch_bounds__(256) void vc_pre_generic_kernel(const VcDims d, con
             if (cond_only) si = CND(VC_SITE_SHAPE_INV) ? b.cnd[VC_SITE_SHAPE_INV][g] : 1.f;
             else {
               si = CND(VC_SITE_SHAPE_INV) ? b.cnd[VC_SITE_SHAPE_INV][g] : expf(P[d.poff[VC_P_SHAPE_INV_ULOCS] + g]);
-              logp += d.gamma_alpha * logf(d.gamma_beta) + (d.gamma_alpha - 1.f) * logf(si) - d.gamma_beta * si - d.lgamma_alpha;
+              logp += vc_gamma_lp(d, si);
               b.lat[VC_SITE_SHAPE_INV][g] = si;
             }
           }
@@ -304,10 +306,11 @@ __global__ __launch_bounds__(256) void vc_pre_generic_kernel(const VcDims d, con
             const float eg = eps(d.eoff[VC_E_LOGGAMMA] + g, d.eoff[VC_E_LOGGAMMA] + g);
             const float eb = eps(d.eoff[VC_E_LOGBETA] + g, d.eoff[VC_E_LOGBETA] + g);
             const float ug = P[d.poff[VC_P_LOGGAMMA_USCALES] + g], ub = P[d.poff[VC_P_LOGBETA_USCALES] + g];
-            lg_guide = P[d.poff[VC_P_LOGGAMMA_LOCS] + g] + expf(ug) * eg;
-            lb_guide = P[d.poff[VC_P_LOGBETA_LOCS] + g] + expf(ub) * eb;
-            if (!CND(VC_SITE_LOGGAMMA)) logq += -0.5f * eg * eg - ug - 0.5f * VC_LOG_2PI;
-            if (!CND(VC_SITE_LOGBETA)) logq += -0.5f * eb * eb - ub - 0.5f * VC_LOG_2PI;
+            float lqg, lqb;
+            lg_guide = vc_mf_draw(P[d.poff[VC_P_LOGGAMMA_LOCS] + g], ug, eg, lqg);
+            lb_guide = vc_mf_draw(P[d.poff[VC_P_LOGBETA_LOCS] + g], ub, eb, lqb);
+            if (!CND(VC_SITE_LOGGAMMA)) logq += lqg;
+            if (!CND(VC_SITE_LOGBETA)) logq += lqb;
           } else {
             // LowRankMultivariateNormal.rsample: X = loc + W eps_W + sqrt(cov_diag) eps_D, any rank
             float delta = 0.f, w2 = 0.f;
@@ -317,21 +320,18 @@ __global__ __launch_bounds__(256) void vc_pre_generic_kernel(const VcDims d, con
               delta += w * ew;
               w2 += w * w;
             }
-            const float dg = expf(P[d.poff[VC_P_LRMN_UCOV_DIAG] + g]);
+            const float ud = P[d.poff[VC_P_LRMN_UCOV_DIAG] + g];
             const float ed = eps(d.eoff[VC_E_LRMN_D] + g, d.eoff[VC_E_LRMN_D] + g);
-            delta += sqrtf(dg) * ed;
-            const float sgam = sqrtf(w2 + dg);
-            lg_guide = P[d.poff[VC_P_LRMN_LOC] + g] + delta;
+            const float loc = P[d.poff[VC_P_LRMN_LOC] + g];
             const float rho_real_g = P[d.poff[VC_P_RHO_REAL_LOC] + g];
-            const float rho = sigmoidf_(rho_real_g / d.rho_scale) * 1.998f - 0.999f;
             const float ub = P[d.poff[VC_P_LOGBETA_USCALES] + g];
-            const float sb = expf(ub);
             const float eb = eps(d.eoff[VC_E_LOGBETA] + g, d.eoff[VC_E_LOGBETA] + g);
-            const float tt = sb * sqrtf(1.f - rho * rho);
-            lb_guide = P[d.poff[VC_P_LOGBETA_LOCS] + g] + rho * sb * delta / sgam + tt * eb;
-            if (!CND(VC_SITE_LOGBETA)) logq += -0.5f * eb * eb - logf(tt) - 0.5f * VC_LOG_2PI;
-            b.lat_delta[g] = delta;
-            b.lat_sgam[g] = sgam;
+            const VcLrmnDraw q = vc_lrmn_draw(d, delta, w2, ud, ed, loc, P[d.poff[VC_P_LOGBETA_LOCS] + g], ub, rho_real_g, eb);
+            lg_guide = q.lg;
+            lb_guide = q.lb;
+            if (!CND(VC_SITE_LOGBETA)) logq += q.lq;
+            b.lat_delta[g] = q.delta;
+            b.lat_sgam[g] = q.sgam;
             const float rho_val = CND(VC_SITE_RHO_REAL) ? b.cnd[VC_SITE_RHO_REAL][g] : rho_real_g;
             logp += vc_normal_lp(rho_val, d.rho_mean, d.rho_std);
             b.lat[VC_SITE_RHO_REAL][g] = rho_val;
@@ -357,8 +357,7 @@ __global__ __launch_bounds__(256) void vc_pre_generic_kernel(const VcDims d, con
           if (!lrmn) {
             const float e = eps(d.eoff[VC_E_NUOMEGA] + j, d.eoff[VC_E_NUOMEGA] + j);
             const float u = P[d.poff[VC_P_NUOMEGA_USCALES] + j];
-            val = P[d.poff[VC_P_NUOMEGA_LOCS] + j] + expf(u) * e;
-            lq = -0.5f * e * e - u - 0.5f * VC_LOG_2PI;
+            val = vc_mf_draw(P[d.poff[VC_P_NUOMEGA_LOCS] + j], u, e, lq);
           } else {
             const long long i = (long long)d.Ng + j;
             float delta = 0.f;
@@ -367,8 +366,8 @@ __global__ __launch_bounds__(256) void vc_pre_generic_kernel(const VcDims d, con
               delta += expf(P[d.poff[VC_P_LRMN_UCOV_FACTOR] + i * d.R + k]) * ew;
             }
             const float ed = eps(d.eoff[VC_E_LRMN_D] + i, d.eoff[VC_E_LRMN_D] + i);
-            delta += sqrtf(expf(P[d.poff[VC_P_LRMN_UCOV_DIAG] + i])) * ed;
-            val = P[d.poff[VC_P_LRMN_LOC] + i] + delta;
+            const float ud = P[d.poff[VC_P_LRMN_UCOV_DIAG] + i];
+            val = vc_lrmn_row_draw(P[d.poff[VC_P_LRMN_LOC] + i], delta, ud, ed, delta);
             if (bc == 0) b.lat_delta[i] = delta;
           }
           const float x = CND(VC_SITE_NUOMEGA) ? b.cnd[VC_SITE_NUOMEGA][j] : val;
@@ -396,12 +395,11 @@ __global__ __launch_bounds__(256) void vc_pre_generic_kernel(const VcDims d, con
         const float px = b.pxy[2 * c], py = b.pxy[2 * c + 1];
         if (CND(VC_SITE_PHIXY)) {
           x = b.cnd[VC_SITE_PHIXY][2 * c]; y = b.cnd[VC_SITE_PHIXY][2 * c + 1];
-          loss += 0.5 * ((double)(x - px) * (x - px) + (double)(y - py) * (y - py)) + (double)VC_LOG_2PI;
         } else {
           x = P[d.poff[VC_P_PHIXY_LOCS] + 2LL * c] + ex;
           y = P[d.poff[VC_P_PHIXY_LOCS] + 2LL * c + 1] + ey;
-          loss += 0.5 * ((double)(x - px) * (x - px) + (double)(y - py) * (y - py)) - 0.5 * ((double)ex * ex + (double)ey * ey);
         }
+        loss += vc_phixy_loss(x, y, px, py, ex, ey, CND(VC_SITE_PHIXY));
         b.lat[VC_SITE_PHIXY][2 * c] = x;
         b.lat[VC_SITE_PHIXY][2 * c + 1] = y;
       }
@@ -492,10 +490,9 @@ __global__ __launch_bounds__(256) void vc_post_generic_kernel(const VcDims d, co
         const long long j = (long long)g * Nh + h;
         float gl = 0.f, gu = 0.f;
         if (!CND(VC_SITE_NU)) {
-          const float x = b.lat[VC_SITE_NU][j], sd = b.sd_nu[j];
-          const float gx = T(h) - rw * (x - b.mu_nu[j]) / (sd * sd);
+          const float gx = vc_prior_grad(T(h), b.lat[VC_SITE_NU][j], b.mu_nu[j], b.sd_nu[j], rw);
           gl = -gx;
-          gu = -gx * expf(P[d.poff[VC_P_NU_USCALES] + j]) * b.eps_used[d.eoff[VC_E_NU] + j] - rw;
+          gu = vc_mf_uscale_grad(gx, P[d.poff[VC_P_NU_USCALES] + j], b.eps_used[d.eoff[VC_E_NU] + j], rw);
         }
         G[d.poff[VC_P_NU_LOCS] + j] = gl;
         G[d.poff[VC_P_NU_USCALES] + j] = gu;
@@ -503,10 +500,7 @@ __global__ __launch_bounds__(256) void vc_post_generic_kernel(const VcDims d, co
       for (int q = 0; q < d.Nb && d.with_dnu; ++q) {
         const long long j = (long long)q * d.Ng + g;
         float gl = 0.f;
-        if (!CND(VC_SITE_DNU)) {
-          const float x = b.lat[VC_SITE_DNU][j], sd = vel ? 0.01f : b.sd_dnu[j];
-          gl = -(T(Nh + q) - rw * x / (sd * sd));
-        }
+        if (!CND(VC_SITE_DNU)) gl = -vc_prior_grad(T(Nh + q), b.lat[VC_SITE_DNU][j], 0.f, vel ? 0.01f : b.sd_dnu[j], rw);
         G[d.poff[VC_P_DNU_LOCS] + j] = gl;
       }
       if (nb) {
@@ -522,46 +516,32 @@ __global__ __launch_bounds__(256) void vc_post_generic_kernel(const VcDims d, co
       if (vel) {
         const float gam = b.GT[(size_t)(K + 1) * NP + g];
         float U_lb, U_lg;
-        if (d.kind == VC_KIND_VFULL) { U_lb = -T(K); U_lg = T(K + 1) * gam; }
-        else { U_lb = -T(0); U_lg = T(1) * gam; }
+        vc_lb_lg_lik(d.kind, K, gam, T, U_lb, U_lg);
         float g_lg = 0.f, g_lb = 0.f;
-        if (!CND(VC_SITE_LOGGAMMA)) { const float sd = b.sd_g[g]; g_lg = U_lg - rw * (b.lat[VC_SITE_LOGGAMMA][g] - b.mu_g[g]) / (sd * sd); }
-        if (!CND(VC_SITE_LOGBETA)) { const float sd = b.sd_b[g]; g_lb = U_lb - rw * (b.lat[VC_SITE_LOGBETA][g] - b.mu_b[g]) / (sd * sd); }
+        if (!CND(VC_SITE_LOGGAMMA)) g_lg = vc_prior_grad(U_lg, b.lat[VC_SITE_LOGGAMMA][g], b.mu_g[g], b.sd_g[g], rw);
+        if (!CND(VC_SITE_LOGBETA)) g_lb = vc_prior_grad(U_lb, b.lat[VC_SITE_LOGBETA][g], b.mu_b[g], b.sd_b[g], rw);
         if (!lrmn) {
           const float eg = b.eps_used[d.eoff[VC_E_LOGGAMMA] + g], eb = b.eps_used[d.eoff[VC_E_LOGBETA] + g];
           const bool cg = CND(VC_SITE_LOGGAMMA), cb = CND(VC_SITE_LOGBETA);
           G[d.poff[VC_P_LOGGAMMA_LOCS] + g] = -g_lg;
-          G[d.poff[VC_P_LOGGAMMA_USCALES] + g] = cg ? 0.f : -g_lg * expf(P[d.poff[VC_P_LOGGAMMA_USCALES] + g]) * eg - rw;
+          G[d.poff[VC_P_LOGGAMMA_USCALES] + g] = cg ? 0.f : vc_mf_uscale_grad(g_lg, P[d.poff[VC_P_LOGGAMMA_USCALES] + g], eg, rw);
           G[d.poff[VC_P_LOGBETA_LOCS] + g] = -g_lb;
-          G[d.poff[VC_P_LOGBETA_USCALES] + g] = cb ? 0.f : -g_lb * expf(P[d.poff[VC_P_LOGBETA_USCALES] + g]) * eb - rw;
+          G[d.poff[VC_P_LOGBETA_USCALES] + g] = cb ? 0.f : vc_mf_uscale_grad(g_lb, P[d.poff[VC_P_LOGBETA_USCALES] + g], eb, rw);
         } else {
-          const bool cb = CND(VC_SITE_LOGBETA);
-          const float A = g_lb;
-          const float ent = cb ? 0.f : rw;
           const float delta = b.lat_delta[g], sgam = b.lat_sgam[g];
-          const float sb = expf(P[d.poff[VC_P_LOGBETA_USCALES] + g]);
           const float rho_real = P[d.poff[VC_P_RHO_REAL_LOC] + g];
-          const float sg = sigmoidf_(rho_real / d.rho_scale);
-          const float rho = sg * 1.998f - 0.999f;
-          const float om = 1.f - rho * rho, sq = sqrtf(om);
-          const float dl_ddelta = -g_lg - A * rho * sb / sgam;
-          const float dl_dsg = A * rho * sb * delta / (sgam * sgam);
-          const float eb = b.eps_used[d.eoff[VC_E_LOGBETA] + g];
-          G[d.poff[VC_P_LOGBETA_LOCS] + g] = -A;
-          G[d.poff[VC_P_LOGBETA_USCALES] + g] = -A * (rho * delta / sgam + sq * eb) * sb - ent;
-          float g_rho = -A * (sb * delta / sgam - sb * rho * eb / sq) + ent * rho / om;
-          float g_rr = g_rho * 1.998f * sg * (1.f - sg) / d.rho_scale;
-          if (!CND(VC_SITE_RHO_REAL)) g_rr += rw * (rho_real - d.rho_mean) / (d.rho_std * d.rho_std);
-          G[d.poff[VC_P_RHO_REAL_LOC] + g] = g_rr;
-          G[d.poff[VC_P_LRMN_LOC] + g] = -g_lg;
-          const float dg = expf(P[d.poff[VC_P_LRMN_UCOV_DIAG] + g]);
-          const float ed = b.eps_used[d.eoff[VC_E_LRMN_D] + g];
-          G[d.poff[VC_P_LRMN_UCOV_DIAG] + g] = (dl_ddelta * ed / (2.f * sqrtf(dg)) + dl_dsg / (2.f * sgam)) * dg;
+          const VcLrmnChain ch = vc_lrmn_chain(d, g_lg, g_lb, delta, sgam, P[d.poff[VC_P_LOGBETA_USCALES] + g], rho_real);
+          const VcLrmnCoreGrad cg = vc_lrmn_core_grad(d, ch, g_lg, g_lb, CND(VC_SITE_LOGBETA), CND(VC_SITE_RHO_REAL), delta, sgam, rho_real,
+                                                      b.eps_used[d.eoff[VC_E_LOGBETA] + g], P[d.poff[VC_P_LRMN_UCOV_DIAG] + g],
+                                                      b.eps_used[d.eoff[VC_E_LRMN_D] + g], rw);
+          G[d.poff[VC_P_LOGBETA_LOCS] + g] = cg.loc_b;
+          G[d.poff[VC_P_LOGBETA_USCALES] + g] = cg.uscale_b;
+          G[d.poff[VC_P_RHO_REAL_LOC] + g] = cg.rho_real;
+          G[d.poff[VC_P_LRMN_LOC] + g] = cg.loc;
+          G[d.poff[VC_P_LRMN_UCOV_DIAG] + g] = cg.udiag;
           for (int k = 0; k < d.R; ++k) {
             const long long j = d.poff[VC_P_LRMN_UCOV_FACTOR] + (long long)g * d.R + k;
-            const float w = expf(P[j]);
-            const float ew = b.eps_used[d.eoff[VC_E_LRMN_W] + k];
-            G[j] = (w > 0.f) ? (dl_ddelta * ew + dl_dsg * w / sgam) * w : 0.f;
+            G[j] = vc_lrmn_cov_grad(ch, sgam, P[j], b.eps_used[d.eoff[VC_E_LRMN_W] + k]);
           }
         }
       }
@@ -581,17 +561,12 @@ __global__ __launch_bounds__(256) void vc_post_generic_kernel(const VcDims d, co
     for (int gb = 0; gb < d.nGB; ++gb)
       for (int j = 0; j < d.nco; ++j) A[j] += b.CO[((size_t)gb * d.nco + j) * d.Nc + c];
     if (d.poff[VC_P_PHIXY_LOCS] >= 0) {
-      float gx = 0.f, gy = 0.f;
-      if (!CND(VC_SITE_PHIXY)) {
-        float dphi = A[0];
-        if (d.kind == VC_KIND_VFULL) dphi += b.lat_omega[c] * A[1] + A[2] * b.lat_domega[c];
-        const float x = b.lat[VC_SITE_PHIXY][2 * c], y = b.lat[VC_SITE_PHIXY][2 * c + 1];
-        const float inv = 1.0f / (x * x + y * y);
-        gx = -(dphi * (-y * inv) - (x - b.pxy[2 * c]));
-        gy = -(dphi * (x * inv) - (y - b.pxy[2 * c + 1]));
-      }
-      G[d.poff[VC_P_PHIXY_LOCS] + 2LL * c] = gx;
-      G[d.poff[VC_P_PHIXY_LOCS] + 2LL * c + 1] = gy;
+      float2 gxy = make_float2(0.f, 0.f);
+      if (!CND(VC_SITE_PHIXY))
+        gxy = vc_phixy_grad(d.kind, A, d.kind == VC_KIND_VFULL ? b.lat_omega[c] : 0.f, d.kind == VC_KIND_VFULL ? b.lat_domega[c] : 0.f,
+                            b.lat[VC_SITE_PHIXY][2 * c], b.lat[VC_SITE_PHIXY][2 * c + 1], b.pxy[2 * c], b.pxy[2 * c + 1]);
+      G[d.poff[VC_P_PHIXY_LOCS] + 2LL * c] = gxy.x;
+      G[d.poff[VC_P_PHIXY_LOCS] + 2LL * c + 1] = gxy.y;
     }
   }
   if (vel) {
@@ -660,24 +635,18 @@ __global__ __launch_bounds__(256) void vc_fin_generic_kernel(const VcDims d, con
   for (int tt = t; tt < d.NW * fin_per; tt += 256) {
     const int j = tt / fin_per, c = tt % fin_per;
     float gx = 0.f;
-    if (!cnd) {
-      const float x = b.lat[VC_SITE_NUOMEGA][j], sd = b.sd_w[j];
-      gx = s_up[j] - d.root_w * (x - b.mu_w[j]) / (sd * sd);
-    }
+    if (!cnd) gx = vc_prior_grad(s_up[j], b.lat[VC_SITE_NUOMEGA][j], b.mu_w[j], b.sd_w[j], d.root_w);
+    auto put = [&](long long off, long long ei) {
+      G[off] = vc_nuw_elem_grad(lrmn, d.R, c, gx, c > 0 ? P[off] : 0.f, c > 0 ? b.eps_used[ei] : 0.f, cnd, d.root_w);
+    };
     if (!lrmn) {
-      if (c == 0) G[d.poff[VC_P_NUOMEGA_LOCS] + j] = -gx;
-      else G[d.poff[VC_P_NUOMEGA_USCALES] + j] = cnd ? 0.f : -gx * expf(P[d.poff[VC_P_NUOMEGA_USCALES] + j]) * b.eps_used[d.eoff[VC_E_NUOMEGA] + j] - d.root_w;
+      if (c == 0) put(d.poff[VC_P_NUOMEGA_LOCS] + j, 0);
+      else put(d.poff[VC_P_NUOMEGA_USCALES] + j, d.eoff[VC_E_NUOMEGA] + j);
     } else {
       const long long i = (long long)d.Ng + j;
-      if (c == 0) G[d.poff[VC_P_LRMN_LOC] + i] = -gx;
-      else if (c <= d.R) {
-        const long long q = d.poff[VC_P_LRMN_UCOV_FACTOR] + i * d.R + (c - 1);
-        const float w = expf(P[q]);
-        G[q] = (w > 0.f) ? -gx * b.eps_used[d.eoff[VC_E_LRMN_W] + (c - 1)] * w : 0.f;
-      } else {
-        const float dg = expf(P[d.poff[VC_P_LRMN_UCOV_DIAG] + i]);
-        G[d.poff[VC_P_LRMN_UCOV_DIAG] + i] = -gx * b.eps_used[d.eoff[VC_E_LRMN_D] + i] / (2.f * sqrtf(dg)) * dg;
-      }
+      if (c == 0) put(d.poff[VC_P_LRMN_LOC] + i, 0);
+      else if (c <= d.R) put(d.poff[VC_P_LRMN_UCOV_FACTOR] + i * d.R + (c - 1), d.eoff[VC_E_LRMN_W] + (c - 1));
+      else put(d.poff[VC_P_LRMN_UCOV_DIAG] + i, d.eoff[VC_E_LRMN_D] + i);
     }
   }
 }

@@ -15,6 +15,7 @@
 #include "vc_common.h"
 #include "vc_tail_spec.h"
 #include "vc_host_logic.h"     // VC_HIST_CAP
+#include "vc_site_math.h"
 
 
 // ---------------------------------------------------------------------------------------------
@@ -234,9 +235,10 @@ __global__ __launch_bounds__(256) void vc_pre_kernel(const VcDims d, const VcBuf
             } else {
               const float e = vc_eps(eps_in, b.eps_used, seed, step, d.eoff[VC_E_NU] + j, d.eoff[VC_E_NU] + j);
               const float u = P[d.poff[VC_P_NU_USCALES] + j];
-              const float xg = P[d.poff[VC_P_NU_LOCS] + j] + expf(u) * e;
+              float lq;
+              const float xg = vc_mf_draw(P[d.poff[VC_P_NU_LOCS] + j], u, e, lq);
               if (CND(VC_SITE_NU)) x = b.cnd[VC_SITE_NU][j];
-              else { x = xg; logq += -0.5f * e * e - u - 0.5f * VC_LOG_2PI; }
+              else { x = xg; logq += lq; }
               logp += vc_normal_lp(x, b.mu_nu[j], b.sd_nu[j]);
               b.lat[VC_SITE_NU][j] = x;
             }
@@ -262,8 +264,7 @@ __global__ __launch_bounds__(256) void vc_pre_kernel(const VcDims d, const VcBuf
               if (cond_only) si = CND(VC_SITE_SHAPE_INV) ? b.cnd[VC_SITE_SHAPE_INV][g] : 1.f;
               else {
                 si = CND(VC_SITE_SHAPE_INV) ? b.cnd[VC_SITE_SHAPE_INV][g] : expf(P[d.poff[VC_P_SHAPE_INV_ULOCS] + g]);
-                logp += d.gamma_alpha * logf(d.gamma_beta) + (d.gamma_alpha - 1.f) * logf(si) -
-                        d.gamma_beta * si - d.lgamma_alpha;
+                logp += vc_gamma_lp(d, si);
                 b.lat[VC_SITE_SHAPE_INV][g] = si;
               }
             }
@@ -277,10 +278,11 @@ __global__ __launch_bounds__(256) void vc_pre_kernel(const VcDims d, const VcBuf
                 const float eg = vc_eps(eps_in, b.eps_used, seed, step, d.eoff[VC_E_LOGGAMMA] + g, d.eoff[VC_E_LOGGAMMA] + g);
                 const float eb = vc_eps(eps_in, b.eps_used, seed, step, d.eoff[VC_E_LOGBETA] + g, d.eoff[VC_E_LOGBETA] + g);
                 const float ug = P[d.poff[VC_P_LOGGAMMA_USCALES] + g], ub = P[d.poff[VC_P_LOGBETA_USCALES] + g];
-                lg_guide = P[d.poff[VC_P_LOGGAMMA_LOCS] + g] + expf(ug) * eg;
-                lb_guide = P[d.poff[VC_P_LOGBETA_LOCS] + g] + expf(ub) * eb;
-                if (!CND(VC_SITE_LOGGAMMA)) logq += -0.5f * eg * eg - ug - 0.5f * VC_LOG_2PI;
-                if (!CND(VC_SITE_LOGBETA)) logq += -0.5f * eb * eb - ub - 0.5f * VC_LOG_2PI;
+                float lqg, lqb;
+                lg_guide = vc_mf_draw(P[d.poff[VC_P_LOGGAMMA_LOCS] + g], ug, eg, lqg);
+                lb_guide = vc_mf_draw(P[d.poff[VC_P_LOGBETA_LOCS] + g], ub, eb, lqb);
+                if (!CND(VC_SITE_LOGGAMMA)) logq += lqg;
+                if (!CND(VC_SITE_LOGBETA)) logq += lqb;
               } else {
                 // LowRankMultivariateNormal.rsample: X = loc + W eps_W + sqrt(cov_diag) eps_D
                 // columns 0..3 and 4..7 are summed separately and then added: the association the fused step uses
@@ -294,21 +296,18 @@ __global__ __launch_bounds__(256) void vc_pre_kernel(const VcDims d, const VcBuf
                     else { delta_hi += w * ew_all[k]; w2_hi += w * w; }
                   }
                 if (d.R > 4) { delta += delta_hi; w2 += w2_hi; }
-                const float dg = expf(P[d.poff[VC_P_LRMN_UCOV_DIAG] + g]);
+                const float ud = P[d.poff[VC_P_LRMN_UCOV_DIAG] + g];
                 const float ed = vc_eps(eps_in, b.eps_used, seed, step, d.eoff[VC_E_LRMN_D] + g, d.eoff[VC_E_LRMN_D] + g);
-                delta += sqrtf(dg) * ed;
-                const float sgam = sqrtf(w2 + dg);
-                lg_guide = P[d.poff[VC_P_LRMN_LOC] + g] + delta;
+                const float loc = P[d.poff[VC_P_LRMN_LOC] + g];
                 const float rho_real_g = P[d.poff[VC_P_RHO_REAL_LOC] + g];
-                const float rho = sigmoidf_(rho_real_g / d.rho_scale) * 1.998f - 0.999f;
                 const float ub = P[d.poff[VC_P_LOGBETA_USCALES] + g];
-                const float sb = expf(ub);
                 const float eb = vc_eps(eps_in, b.eps_used, seed, step, d.eoff[VC_E_LOGBETA] + g, d.eoff[VC_E_LOGBETA] + g);
-                const float tt = sb * sqrtf(1.f - rho * rho);
-                lb_guide = P[d.poff[VC_P_LOGBETA_LOCS] + g] + rho * sb * delta / sgam + tt * eb;
-                if (!CND(VC_SITE_LOGBETA)) logq += -0.5f * eb * eb - logf(tt) - 0.5f * VC_LOG_2PI;
-                b.lat_delta[g] = delta;
-                b.lat_sgam[g] = sgam;
+                const VcLrmnDraw q = vc_lrmn_draw(d, delta, w2, ud, ed, loc, P[d.poff[VC_P_LOGBETA_LOCS] + g], ub, rho_real_g, eb);
+                lg_guide = q.lg;
+                lb_guide = q.lb;
+                if (!CND(VC_SITE_LOGBETA)) logq += q.lq;
+                b.lat_delta[g] = q.delta;
+                b.lat_sgam[g] = q.sgam;
                 const float rho_val = CND(VC_SITE_RHO_REAL) ? b.cnd[VC_SITE_RHO_REAL][g] : rho_real_g;
                 logp += vc_normal_lp(rho_val, d.rho_mean, d.rho_std);
                 b.lat[VC_SITE_RHO_REAL][g] = rho_val;
@@ -336,8 +335,7 @@ __global__ __launch_bounds__(256) void vc_pre_kernel(const VcDims d, const VcBuf
         if (!lrmn) {
           const float e = vc_eps(eps_in, b.eps_used, seed, step, d.eoff[VC_E_NUOMEGA] + j, d.eoff[VC_E_NUOMEGA] + j);
           const float u = P[d.poff[VC_P_NUOMEGA_USCALES] + j];
-          val = P[d.poff[VC_P_NUOMEGA_LOCS] + j] + expf(u) * e;
-          lq = -0.5f * e * e - u - 0.5f * VC_LOG_2PI;
+          val = vc_mf_draw(P[d.poff[VC_P_NUOMEGA_LOCS] + j], u, e, lq);
         } else {
           const long long i = (long long)d.Ng + j;
           float delta = 0.f;
@@ -347,8 +345,8 @@ __global__ __launch_bounds__(256) void vc_pre_kernel(const VcDims d, const VcBuf
             delta += expf(P[d.poff[VC_P_LRMN_UCOV_FACTOR] + i * d.R + k]) * ew;
           }
           const float ed = vc_eps(eps_in, b.eps_used, seed, step, d.eoff[VC_E_LRMN_D] + i, d.eoff[VC_E_LRMN_D] + i);
-          delta += sqrtf(expf(P[d.poff[VC_P_LRMN_UCOV_DIAG] + i])) * ed;
-          val = P[d.poff[VC_P_LRMN_LOC] + i] + delta;
+          const float ud = P[d.poff[VC_P_LRMN_UCOV_DIAG] + i];
+          val = vc_lrmn_row_draw(P[d.poff[VC_P_LRMN_LOC] + i], delta, ud, ed, delta);
           if (bc == 0) b.lat_delta[i] = delta;
         }
         const float x = CND(VC_SITE_NUOMEGA) ? b.cnd[VC_SITE_NUOMEGA][j] : val;
@@ -376,14 +374,11 @@ __global__ __launch_bounds__(256) void vc_pre_kernel(const VcDims d, const VcBuf
         const float px = b.pxy[2 * c], py = b.pxy[2 * c + 1];
         if (CND(VC_SITE_PHIXY)) {
           x = b.cnd[VC_SITE_PHIXY][2 * c]; y = b.cnd[VC_SITE_PHIXY][2 * c + 1];
-          loss += 0.5 * ((double)(x - px) * (x - px) + (double)(y - py) * (y - py)) + (double)VC_LOG_2PI;
         } else {
           x = P[d.poff[VC_P_PHIXY_LOCS] + 2LL * c] + ex;
           y = P[d.poff[VC_P_PHIXY_LOCS] + 2LL * c + 1] + ey;
-          // -(log p - log q): the -log(2 pi) of prior and guide cancel
-          loss += 0.5 * ((double)(x - px) * (x - px) + (double)(y - py) * (y - py)) -
-                  0.5 * ((double)ex * ex + (double)ey * ey);
         }
+        loss += vc_phixy_loss(x, y, px, py, ex, ey, CND(VC_SITE_PHIXY));
         b.lat[VC_SITE_PHIXY][2 * c] = x;
         b.lat[VC_SITE_PHIXY][2 * c + 1] = y;
       }
@@ -391,12 +386,7 @@ __global__ __launch_bounds__(256) void vc_pre_kernel(const VcDims d, const VcBuf
       float s1, c1;
       vc_dir_sincos(x, y, &s1, &c1);
       float sk[VC_MAXH], ck[VC_MAXH];
-      sk[0] = s1; ck[0] = c1;
-      const int hm = d.H > d.Hw ? d.H : d.Hw;
-      for (int k = 1; k < hm && k < VC_MAXH; ++k) {
-        sk[k] = sk[k - 1] * c1 + ck[k - 1] * s1;
-        ck[k] = ck[k - 1] * c1 - sk[k - 1] * s1;
-      }
+      vc_harmonics(s1, c1, d.H > d.Hw ? d.H : d.Hw, sk, ck);
       float omega = 0.f, domega = 0.f;
       if (vel && !cond_only) {
         for (int xq = 0; xq < d.Nx; ++xq) {
@@ -496,8 +486,6 @@ void vc_launch_particle_avg(const VcParticleGrads& pg, long long n, double* loss
 // ---------------------------------------------------------------------------------------------
 // K_post_gene: 1024 threads = 16 waves; lanes = 64 genes; wave w sums chunks w, w+16, ...
 // ---------------------------------------------------------------------------------------------
-#define VC_PG_WAVES 16
-#define VC_MAXQ (2 * VC_MAXH + 1 + VC_MAXNB + 3)
 // MQ = compiled bound of the number of partial-sum rows (nq): 2 (U-only kernel), 6 (S+U kernel with H = 1, no batches;
 // phase up to K = 5) or VC_MAXQ; the reduction loop keeps 4 x MQ loads in flight, so the small variants leave registers
 // for the role inputs that are fetched ahead of it.
@@ -612,10 +600,9 @@ __device__ __forceinline__ void vc_post_gene_block(const VcDims& d, const VcBufs
       const long long j = (long long)g * Nh + h;
       float gl = 0.f, gu = 0.f;
       if (!CND(VC_SITE_NU)) {
-        const float x = in[0], sd = in[1];
-        const float gx = T(h) - rw * (x - in[2]) / (sd * sd);
+        const float gx = vc_prior_grad(T(h), in[0], in[2], in[1], rw);
         gl = -gx;
-        gu = -gx * expf(in[4]) * in[3] - rw;
+        gu = vc_mf_uscale_grad(gx, in[4], in[3], rw);
       }
       G[d.poff[VC_P_NU_LOCS] + j] = gl;
       G[d.poff[VC_P_NU_USCALES] + j] = gu;
@@ -624,10 +611,7 @@ __device__ __forceinline__ void vc_post_gene_block(const VcDims& d, const VcBufs
       const int q = role - Nh;
       const long long j = (long long)q * d.Ng + g;
       float gl = 0.f;
-      if (!CND(VC_SITE_DNU)) {
-        const float x = in[0], sd = in[1];
-        gl = -(T(Nh + q) - rw * x / (sd * sd));
-      }
+      if (!CND(VC_SITE_DNU)) gl = -vc_prior_grad(T(Nh + q), in[0], 0.f, in[1], rw);
       G[d.poff[VC_P_DNU_LOCS] + j] = gl;
     } else if (role >= Nh && role < 12 && d.onehot) {
       // ---- delta nu[q], one-hot batches: q = role - Nh, + (12 - Nh), ... ; the likelihood part is the constant harmonic's
@@ -646,7 +630,7 @@ __device__ __forceinline__ void vc_post_gene_block(const VcDims& d, const VcBufs
           } else {
             lik = vc_dnu_range_sum(d, b, g, q);
           }
-          gl = -(lik - rw * x / (sd * sd));
+          gl = -vc_prior_grad(lik, x, 0.f, sd, rw);
         }
         G[d.poff[VC_P_DNU_LOCS] + j] = gl;
       }
@@ -668,53 +652,37 @@ __device__ __forceinline__ void vc_post_gene_block(const VcDims& d, const VcBufs
       // ---- log gamma / log beta ----
       const float gam = in[0];
       float U_lb, U_lg;
-      if (d.kind == VC_KIND_VFULL) { U_lb = -T(K); U_lg = T(K + 1) * gam; }
-      else { U_lb = -T(0); U_lg = T(1) * gam; }
+      vc_lb_lg_lik(d.kind, K, gam, T, U_lb, U_lg);
       float g_lg = 0.f, g_lb = 0.f;   // total d log p / d site (0 when the site is conditioned)
-      if (!CND(VC_SITE_LOGGAMMA)) g_lg = U_lg - rw * (in[1] - in[3]) / (in[2] * in[2]);
-      if (!CND(VC_SITE_LOGBETA)) g_lb = U_lb - rw * (in[4] - in[6]) / (in[5] * in[5]);
+      if (!CND(VC_SITE_LOGGAMMA)) g_lg = vc_prior_grad(U_lg, in[1], in[3], in[2], rw);
+      if (!CND(VC_SITE_LOGBETA)) g_lb = vc_prior_grad(U_lb, in[4], in[6], in[5], rw);
       if (!lrmn) {
         if (role == 13) {
           const float eg = in[7], eb = in[8];
           const bool cg = CND(VC_SITE_LOGGAMMA), cb = CND(VC_SITE_LOGBETA);
           G[d.poff[VC_P_LOGGAMMA_LOCS] + g] = -g_lg;
-          G[d.poff[VC_P_LOGGAMMA_USCALES] + g] = cg ? 0.f : -g_lg * expf(in[9]) * eg - rw;
+          G[d.poff[VC_P_LOGGAMMA_USCALES] + g] = cg ? 0.f : vc_mf_uscale_grad(g_lg, in[9], eg, rw);
           G[d.poff[VC_P_LOGBETA_LOCS] + g] = -g_lb;
-          G[d.poff[VC_P_LOGBETA_USCALES] + g] = cb ? 0.f : -g_lb * expf(in[10]) * eb - rw;
+          G[d.poff[VC_P_LOGBETA_USCALES] + g] = cb ? 0.f : vc_mf_uscale_grad(g_lb, in[10], eb, rw);
         }
       } else {
-        // q(log beta | log gamma) = N(a + rho s_b delta / s_gamma, s_b sqrt(1-rho^2)); log gamma = loc + delta
-        const bool cb = CND(VC_SITE_LOGBETA);
-        const float A = g_lb;
-        const float ent = cb ? 0.f : rw;        // weight of the guide's -log(std) term
-        const float delta = in[7], sgam = in[8];
-        const float sb = expf(in[9]);
-        const float rho_real = in[10];
-        const float sg = sigmoidf_(rho_real / d.rho_scale);
-        const float rho = sg * 1.998f - 0.999f;
-        const float om = 1.f - rho * rho, sq = sqrtf(om);
-        const float dl_ddelta = -g_lg - A * rho * sb / sgam;
-        const float dl_dsg = A * rho * sb * delta / (sgam * sgam);
+        // LRMN joint guide of (log gamma, log beta): delta = in[7], s_gamma = in[8], log s_b = in[9], rho_real = in[10]
+        const VcLrmnChain ch = vc_lrmn_chain(d, g_lg, g_lb, in[7], in[8], in[9], in[10]);
         if (role == 13) {
-          const float eb = in[11];
-          G[d.poff[VC_P_LOGBETA_LOCS] + g] = -A;
-          G[d.poff[VC_P_LOGBETA_USCALES] + g] = -A * (rho * delta / sgam + sq * eb) * sb - ent;
-          float g_rho = -A * (sb * delta / sgam - sb * rho * eb / sq) + ent * rho / om;
-          float g_rr = g_rho * 1.998f * sg * (1.f - sg) / d.rho_scale;
-          if (!CND(VC_SITE_RHO_REAL)) g_rr += rw * (rho_real - d.rho_mean) / (d.rho_std * d.rho_std);
-          G[d.poff[VC_P_RHO_REAL_LOC] + g] = g_rr;
-          G[d.poff[VC_P_LRMN_LOC] + g] = -g_lg;
-          const float dg = expf(in[12]);
-          const float ed = in[13];
-          G[d.poff[VC_P_LRMN_UCOV_DIAG] + g] = (dl_ddelta * ed / (2.f * sqrtf(dg)) + dl_dsg / (2.f * sgam)) * dg;
+          const VcLrmnCoreGrad cg = vc_lrmn_core_grad(d, ch, g_lg, g_lb, CND(VC_SITE_LOGBETA), CND(VC_SITE_RHO_REAL), in[7], in[8], in[10],
+                                                      in[11], in[12], in[13], rw);
+          G[d.poff[VC_P_LOGBETA_LOCS] + g] = cg.loc_b;
+          G[d.poff[VC_P_LOGBETA_USCALES] + g] = cg.uscale_b;
+          G[d.poff[VC_P_RHO_REAL_LOC] + g] = cg.rho_real;
+          G[d.poff[VC_P_LRMN_LOC] + g] = cg.loc;
+          G[d.poff[VC_P_LRMN_UCOV_DIAG] + g] = cg.udiag;
         } else {
 #pragma unroll
           for (int k = 0; k < VC_MAX_RANK; ++k)
             if (k < d.R) {
               const long long j = d.poff[VC_P_LRMN_UCOV_FACTOR] + (long long)g * d.R + k;
-              const float w = expf(in[11 + k]);
               const float ew = b.eps_used[d.eoff[VC_E_LRMN_W] + k];          // wave-uniform, a scalar-cache hit
-              G[j] = (w > 0.f) ? (dl_ddelta * ew + dl_dsg * w / sgam) * w : 0.f;
+              G[j] = vc_lrmn_cov_grad(ch, in[8], in[11 + k], ew);
             }
         }
       }
@@ -760,29 +728,17 @@ __device__ __forceinline__ void vc_post_cell_block(const VcDims& d, const VcBufs
       for (int j = 0; j < d.nco; ++j) A[j] += b.CO[((size_t)gb * d.nco + j) * d.Nc + cp];
     VC_KSTAMP(1, 1);
     if (d.poff[VC_P_PHIXY_LOCS] >= 0) {
-      float gx = 0.f, gy = 0.f;
-      if (!CND(VC_SITE_PHIXY)) {
-        float dphi = A[0];
-        if (d.kind == VC_KIND_VFULL) dphi += om * A[1] + A[2] * dom;
-        const float x = xy.x, y = xy.y;
-        const float inv = 1.0f / (x * x + y * y);
-        gx = -(dphi * (-y * inv) - (x - pxy.x));
-        gy = -(dphi * (x * inv) - (y - pxy.y));
-      }
-      G[d.poff[VC_P_PHIXY_LOCS] + 2LL * c] = gx;
-      G[d.poff[VC_P_PHIXY_LOCS] + 2LL * c + 1] = gy;
+      float2 gxy = make_float2(0.f, 0.f);
+      if (!CND(VC_SITE_PHIXY)) gxy = vc_phixy_grad(d.kind, A, om, dom, xy.x, xy.y, pxy.x, pxy.y);
+      G[d.poff[VC_P_PHIXY_LOCS] + 2LL * c] = gxy.x;
+      G[d.poff[VC_P_PHIXY_LOCS] + 2LL * c + 1] = gxy.y;
     }
   }
   if (vel) {
     // partial sums of d loglik / d nu_omega[x,h] = sum_c A3_c D[x,c] zeta_omega_h(phi_c)
     const float a3 = (c < d.Nc) ? (d.kind == VC_KIND_VFULL ? A[2] : A[0]) : 0.f;
-    float s1 = sc1.x, c1 = sc1.y;                 // (the cell record's own sin / cos: the bits K_pre built the basis from)
     float sk[VC_MAXH], ck[VC_MAXH];
-    sk[0] = s1; ck[0] = c1;
-    for (int k = 1; k < d.Hw && k < VC_MAXH; ++k) {
-      sk[k] = sk[k - 1] * c1 + ck[k - 1] * s1;
-      ck[k] = ck[k - 1] * c1 - sk[k - 1] * s1;
-    }
+    vc_harmonics(sc1.x, sc1.y, d.Hw, sk, ck);      // (the cell record's own sin / cos: the bits K_pre built the basis from)
     for (int xq = 0; xq < d.Nx; ++xq) {
       const float dx = (c < d.Nc) ? (xq < 2 ? dx01[xq] : b.Dm[(size_t)xq * d.Nc + c]) : 0.f;
       for (int h = 0; h < d.Nhw; ++h) {
@@ -899,21 +855,16 @@ __device__ __forceinline__ void vc_fin_block(const VcDims& d, const VcBufs& b, c
     const int j = fin_tt / fin_per, c = fin_tt % fin_per;
     const bool cnd = CND(VC_SITE_NUOMEGA);
     float gx = 0.f;
-    if (!cnd) gx = sm_up[j] - d.root_w * (fin_in[0] - fin_in[2]) / (fin_in[1] * fin_in[1]);
+    if (!cnd) gx = vc_prior_grad(sm_up[j], fin_in[0], fin_in[2], fin_in[1], d.root_w);
+    const float gv = vc_nuw_elem_grad(lrmn, d.R, c, gx, fin_in[3], fin_in[4], cnd, d.root_w);
     if (!lrmn) {
-      if (c == 0) G[d.poff[VC_P_NUOMEGA_LOCS] + j] = -gx;
-      else G[d.poff[VC_P_NUOMEGA_USCALES] + j] = cnd ? 0.f : -gx * expf(fin_in[3]) * fin_in[4] - d.root_w;
+      if (c == 0) G[d.poff[VC_P_NUOMEGA_LOCS] + j] = gv;
+      else G[d.poff[VC_P_NUOMEGA_USCALES] + j] = gv;
     } else {
       const long long i = (long long)d.Ng + j;
-      if (c == 0) G[d.poff[VC_P_LRMN_LOC] + i] = -gx;
-      else if (c <= d.R) {
-        const long long q = d.poff[VC_P_LRMN_UCOV_FACTOR] + i * d.R + (c - 1);
-        const float w = expf(fin_in[3]);
-        G[q] = (w > 0.f) ? -gx * fin_in[4] * w : 0.f;
-      } else {
-        const float dg = expf(fin_in[3]);
-        G[d.poff[VC_P_LRMN_UCOV_DIAG] + i] = -gx * fin_in[4] / (2.f * sqrtf(dg)) * dg;
-      }
+      if (c == 0) G[d.poff[VC_P_LRMN_LOC] + i] = gv;
+      else if (c <= d.R) G[d.poff[VC_P_LRMN_UCOV_FACTOR] + i * d.R + (c - 1)] = gv;
+      else G[d.poff[VC_P_LRMN_UCOV_DIAG] + i] = gv;
     }
   }
   // more than 256 output elements (NW * (R + 2) > 256): the rest the plain way
@@ -923,21 +874,15 @@ __device__ __forceinline__ void vc_fin_block(const VcDims& d, const VcBufs& b, c
       const int j = tt / fin_per, c = tt % fin_per;
       const bool cnd = CND(VC_SITE_NUOMEGA);
       float gx = 0.f;
-      if (!cnd) {
-        const float x = b.lat[VC_SITE_NUOMEGA][j], sd = b.sd_w[j];
-        gx = sm_up[j] - d.root_w * (x - b.mu_w[j]) / (sd * sd);
-      }
+      if (!cnd) gx = vc_prior_grad(sm_up[j], b.lat[VC_SITE_NUOMEGA][j], b.mu_w[j], b.sd_w[j], d.root_w);
       const long long i = (long long)d.Ng + j;       // only LRMN reaches here (2 NW <= 128 otherwise)
       if (!lrmn) continue;
-      if (c == 0) G[d.poff[VC_P_LRMN_LOC] + i] = -gx;
-      else if (c <= d.R) {
-        const long long q = d.poff[VC_P_LRMN_UCOV_FACTOR] + i * d.R + (c - 1);
-        const float w = expf(P[q]);
-        G[q] = (w > 0.f) ? -gx * b.eps_used[d.eoff[VC_E_LRMN_W] + (c - 1)] * w : 0.f;
-      } else {
-        const float dg = expf(P[d.poff[VC_P_LRMN_UCOV_DIAG] + i]);
-        G[d.poff[VC_P_LRMN_UCOV_DIAG] + i] = -gx * b.eps_used[d.eoff[VC_E_LRMN_D] + i] / (2.f * sqrtf(dg)) * dg;
-      }
+      auto put = [&](long long off, long long ei) {
+        G[off] = vc_nuw_elem_grad(true, d.R, c, gx, c > 0 ? P[off] : 0.f, c > 0 ? b.eps_used[ei] : 0.f, cnd, d.root_w);
+      };
+      if (c == 0) put(d.poff[VC_P_LRMN_LOC] + i, 0);
+      else if (c <= d.R) put(d.poff[VC_P_LRMN_UCOV_FACTOR] + i * d.R + (c - 1), d.eoff[VC_E_LRMN_W] + (c - 1));
+      else put(d.poff[VC_P_LRMN_UCOV_DIAG] + i, d.eoff[VC_E_LRMN_D] + i);
     }
   }
 }
