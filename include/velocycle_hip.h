@@ -32,6 +32,9 @@
  *                               (velocity_inference_model.py:236-258, phase_inference_model.py:248-262)
  *   vc_read_site                the sampled / deterministic sites a trace exposes
  *                               (pyro.deterministic calls at velocity_inference_model.py:327-369)
+ *   vc_phase_mle                Phases.from_cycle_mle (phases.py:471-509): the log-likelihood of every cell's spliced counts
+ *                               on a grid of phases (ElogS / exp / Poisson | GammaPoisson log_prob / sum over genes, :499-507)
+ *                               and its arg-max per cell (:508); stand-alone, no engine
  */
 #ifndef VELOCYCLE_HIP_H
 #define VELOCYCLE_HIP_H
@@ -224,7 +227,7 @@ typedef struct vc_stats {
 int vc_abi_version(void);
 int vc_create(const vc_config* cfg, vc_engine** out);
 void vc_destroy(vc_engine* e);
-/* message of the last failing call on `e` (or of the last failing vc_create when e == NULL) */
+/* message of the last failing call on `e` (e == NULL: of this thread's last failing vc_create / engine-less call such as vc_phase_mle) */
 const char* vc_last_error(const vc_engine* e);
 
 /* Tuning (optional): after vc_create and before the first vc_set_counts* call; NULL or never calling it = all defaults.
@@ -450,6 +453,29 @@ int vc_sample_posterior(vc_engine* e, const float* params, uint64_t seed, int64_
 int vc_expected_logs(vc_engine* e, const float* nu, const float* dnu, const float* phi, const float* omega,
                      const float* logbeta, const float* gamma, float cf_avg, float* out_S, float* out_S2,
                      float* out_U, float* out_U2, void* hip_stream);
+
+/* --- maximum-likelihood phase assignment on a grid (stand-alone: no engine handle) -----------------------------------------
+ * Replaces the body of Phases.from_cycle_mle (phases.py:487-508): for every cell c and bin j < bins the log-likelihood of the
+ * cell's counts under  mu = exp(T[j,g]) * m[c]  summed over the genes, then the best bin per cell.  The reference materialises
+ * [bins][Ng][Nc] float32 tensors for this; here nothing of that size exists: one launch, no workspace, no allocation, no
+ * synchronisation (asynchronous on hip_stream).  Every pointer is DEVICE memory.
+ *   counts_dev   element (g, c) at index g * gene_stride + c (gene_stride >= Nc); float (VC_COUNTS_F32) or uint16_t (VC_COUNTS_U16)
+ *   T_dev        float[bins][Ng]: zeta(phi_j) . means (natural log units);  expT_dev: its exponential, same layout
+ *   m_dev        float[Nc] > 0: n_c^a (phases.py:492-494)
+ *   noise        VC_NOISE_POISSON | VC_NOISE_NB; VC_NOISE_LOGNORMAL returns VC_ERR_UNSUPPORTED (the reference raises
+ *                NotImplementedError, phases.py:504)
+ *   r_dev        float[Ng] > 0: 1 / dispersion per gene (GammaPoisson(1 / si, 1 / (si mu)), phases.py:503); NULL for Poisson
+ *   best_bin_dev int32[Nc]: arg max over j; of equal bins the FIRST wins (torch.argmax, phases.py:508)
+ *   logp_rel_dev NULL, or float[bins][Nc]: logP[j,c] - max_j logP[j,c] (<= 0, exactly 0 at best_bin): the terms of the
+ *                log-likelihood that do not depend on the bin (lgamma, r log r) cancel in it and are never formed
+ * Magnitudes: the sums are formed from exp(T) + r / m and m / k, so the caller should hand over T and m on comparable scales
+ * (mu is unchanged by T + s, m * exp(-s); velocycle_amd.phase_mle centres T).  bins 1..4096, any Ng >= 1, Nc >= 1.  Results are
+ * bit-reproducible and do not depend on how the caller cuts the cells into calls.  Errors: vc_last_error(NULL). */
+#define VC_COUNTS_F32 0
+#define VC_COUNTS_U16 1
+int vc_phase_mle(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* T_dev,
+                 const float* expT_dev, int bins, const float* m_dev, int noise, const float* r_dev, int32_t* best_bin_dev,
+                 float* logp_rel_dev, void* hip_stream);
 
 /* introspection ----------------------------------------------------------------------------- */
 /* Copies the value a site took in the last vc_elbo_grad to host memory (synchronises the stream). */

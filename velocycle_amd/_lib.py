@@ -21,6 +21,7 @@ VC_ERR_ARG, VC_ERR_HIP, VC_ERR_UNSUPPORTED, VC_ERR_STATE, VC_ERR_NONFINITE = -1,
 MODEL = {"phase": 0, "velocity": 1}
 GUIDE = {"meanfield": 0, "lrmn": 1}
 NOISE = {"NegativeBinomial": 0, "Poisson": 1, "Lognormal": 2}
+VC_COUNTS_F32, VC_COUNTS_U16 = 0, 1
 
 # sample sites, parameters and eps blocks, named as in the reference
 SITES = ["ϕxy", "ν", "Δν", "shape_inv", "logγg", "logβg", "νω", "rho_real"]
@@ -129,6 +130,8 @@ EXPORTS = {
                                       C.c_void_p, C.c_void_p]),
     "vc_expected_logs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vc_phase_mle": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vc_read_site": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "vc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(vc_stats)]),
     "vc_get_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),

@@ -263,6 +263,49 @@ class Phases:
         i = int(np.argmax(np.array(corr)))
         return shifts[i], corr[i], corr
 
+    def from_cycle_mle(self, cycle, data, a=1, bins=100, concentration=10., noisemodel='Poisson', dispersion=0.3, *,
+                       device=None, chunk_cells=None, return_profile=False):
+        """Gives every cell the phase, out of `bins` equally spaced ones, that maximises the likelihood of its spliced counts
+        under the fitted `cycle` (reference phases.py:471-509; in place: `set_phixy(concentration * (cos phi, sin phi))`).
+        The likelihood grid is evaluated by the HIP kernel behind `velocycle_amd.phase_mle.phase_mle`; nothing of size
+        bins x genes x cells is stored.  `dispersion` may also be one value per gene (e.g. a fitted cycle's `disp_pyro`).
+        Keyword-only: `device`, `chunk_cells` (cells per device block; the result does not depend on it),
+        `return_profile=True` returns (best_bin, logP - max logP) as device tensors; otherwise None like the reference."""
+        from .phase_mle import NOISEMODELS, phase_mle
+        from .utils import torch_fourier_basis, unpack_direction
+        if noisemodel not in NOISEMODELS:
+            raise NotImplementedError("Not implemented yet, sorry")
+        if int(bins) != bins or bins < 1:
+            raise ValueError("bins must be an integer >= 1")
+        bins = int(bins)
+        means = np.asarray(cycle.means.values, dtype=np.float64)
+        layer = data.layers['spliced']
+        Nc, Ng = layer.shape
+        genes_c, genes_d = list(cycle.means.columns), list(data.var.index)
+        named = not isinstance(cycle.means.columns, pd.RangeIndex)
+        if means.shape[1] != Ng or (named and genes_c != genes_d):
+            raise ValueError("the genes of the cycle do not match the genes of the data (same genes, same order)")
+        n_scounts = np.asarray(data.obs.n_scounts.values, dtype=np.float64)
+        if not (np.isfinite(n_scounts).all() and (n_scounts > 0).all()):
+            raise ValueError("every cell needs n_scounts > 0")
+        if noisemodel == 'NegativeBinomial' and not (np.asarray(dispersion, dtype=np.float64) > 0).all():
+            raise ValueError("dispersion must be > 0")
+        # the grid exactly as the reference builds it (float32 phases; :495-498), the table itself in float64
+        phis = (2 * np.pi * torch.arange(0, 1, 1. / bins, dtype=torch.float32))[:bins]
+        basis = torch_fourier_basis(phis, num_harmonics=(means.shape[0] - 1) // 2)
+        T = basis.double() @ torch.tensor(means)
+        m = torch.tensor(n_scounts) ** float(a)
+        if not (hasattr(layer, "tocsr") or torch.is_tensor(layer)):
+            layer = np.asarray(layer)
+        best, prof = phase_mle(layer, T, m, noisemodel=noisemodel, dispersion=dispersion, device=device,
+                               chunk_cells=chunk_cells, return_profile=return_profile)
+        xy = (concentration * unpack_direction(phis[best.cpu()])).T
+        if self.phi_xy is None:
+            self.phi_xy = pd.DataFrame(xy.numpy(), index=["phi_x", "phi_y"], columns=data.obs.index)
+        else:
+            self.set_phixy(xy)
+        return (best, prof) if return_profile else None
+
     def shift_zero(self, gene=None, phase=None):
         if gene is not None:
             raise Exception("Error: must phase for desired shift")

@@ -24,6 +24,11 @@ thread_local std::string g_create_error;
 
 }  // namespace
 
+// the engine-less entry points of other translation units (vc_phase_mle.hip) leave their message where vc_last_error(NULL) reads it
+void vc_set_global_error(const char* msg) {
+  try { g_create_error = msg ? msg : ""; } catch (...) {}
+}
+
 // RCCL, bound at run time (vc_comm_init_rccl): the four entry points the sharded step needs.  Declared here instead of
 // including rccl.h so that the library neither links nor requires RCCL (single-GPU use never loads it).
 struct VcNcclId { char internal[128]; };
