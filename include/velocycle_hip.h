@@ -35,6 +35,8 @@
  *   vc_phase_mle                Phases.from_cycle_mle (phases.py:471-509): the log-likelihood of every cell's spliced counts
  *                               on a grid of phases (ElogS / exp / Poisson | GammaPoisson log_prob / sum over genes, :499-507)
  *                               and its arg-max per cell (:508); stand-alone, no engine
+ *   vc_pointwise_density        no counterpart (Predictive + a traced model run per draw would be it): lppd / WAIC of every
+ *                               observed count over posterior draws, summed per gene and per cell
  */
 #ifndef VELOCYCLE_HIP_H
 #define VELOCYCLE_HIP_H
@@ -476,6 +478,42 @@ int vc_expected_logs(vc_engine* e, const float* nu, const float* dnu, const floa
 int vc_phase_mle(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* T_dev,
                  const float* expT_dev, int bins, const float* m_dev, int noise, const float* r_dev, int32_t* best_bin_dev,
                  float* logp_rel_dev, void* hip_stream);
+
+/* --- pointwise predictive density over posterior draws (lppd, WAIC) -------------------------------------------------------
+ * The reference has no function for it (on its stack: Predictive + one traced model run per draw and a [D][Ng][Nc] tensor of
+ * log-probs); the quantity is defined by the reference's own model code (velocity_inference_model.py:338-386,
+ * phase_inference_model.py:343-395).  For draw d (site values as vc_sample_posterior delivers them), gene g, cell c:
+ *   eta_S = nu_d[g,:] . zeta(phi_dc) + sum_b Db[b,c] dnu[b,g] + count_factor[c]
+ *   omega = sum_x sum_h nuomega_d[x,h] zeta_omega_h(phi_dc) D[x,c]                                             (velocity)
+ *   z     = (nu_d[g,:] . zeta'(phi_dc)) omega + exp(loggamma_d[g]);  eta_U = -logbeta_d[g] + log(relu(z) + 1e-5) + eta_S
+ *   NegativeBinomial  l(k; r, eta) = lgamma(r+k) - lgamma(r) - lgamma(k+1) + r log r + k eta - (r+k) log(r + e^eta),  r = 1 / shape_inv[g]
+ *   Poisson           l(k; eta)    = k eta - e^eta - lgamma(k+1)
+ * phi_dc = the angle of the draw's phixy (the basis is formed from the direction, not from the rounded angle).  Per count matrix
+ * M (S; velocity: S then U) and element:
+ *   lppd = log((1/D) sum_d exp l_d)      mean = (1/D) sum_d l_d      pwaic = sum_d (l_d - mean)^2 / (D - 1)
+ * Outputs (DEVICE float64), quantity q = 3 M + {0 lppd, 1 mean, 2 pwaic}:
+ *   gene_out_dev [3 nmat][Ng]        sums over the cells [cell_begin, cell_begin + cell_count), ADDED to what the buffer holds (zero it
+ *                                    before the first call over a set of cells; cut into calls in ascending cell order)
+ *   cell_out_dev [3 nmat][Nc_local]  sums over the genes, written for the cells of the call, in the caller's cell order
+ *   dense_lppd_dev  NULL, or float[nmat][Ng][Nc_local]: lppd per element, written for the cells of the call
+ * Inputs: every pointer is DEVICE memory, draw-major float[n_draws][length of the site] with a draw stride in floats that is the
+ * site's length, or 0 for a site that is the same in every draw (conditioned: hand over one copy).  dnu (Delta site) and shape_inv
+ * (Delta site) cannot vary over draws in this model and have no stride; dnu is NULL without batch offsets, shape_inv for Poisson,
+ * loggamma / logbeta / nuomega for the phase model.  With phixy_stride == 0 and nu_stride == 0 (the tutorials' velocity stage)
+ * the S matrix is evaluated once: its pwaic is exactly 0 and its lppd equals its mean.
+ * The counts are read where vc_finalize put them; the only workspaces are one float64 per histogram entry (the lgamma terms:
+ * formed once per distinct (gene, count) pair in float64, never per draw) and [min(512, ceil(Nc_local / 64))][3 nmat][Ng] float64
+ * of per-gene partial rows, both kept by the engine from the first call on.  All sums are float64 in a fixed order, no atomics:
+ * two calls give the same bits, and so does any cutting of the cells into calls whose cell_begin is a multiple of 64.
+ * Asynchronous on hip_stream; one call at a time per engine.  Supported: what the compiled fast kernel set covers (both models and
+ * guides, NegativeBinomial and Poisson, H 1..3, Hw 0..3, any one-hot batches, the dense design up to 4).  VC_ERR_UNSUPPORTED (with
+ * the reason in vc_last_error) for Lognormal noise and the run-time-sized configurations; VC_ERR_ARG for a NULL engine (message:
+ * vc_last_error(NULL)), n_draws < 2, a NULL output or input, a stride or cell range out of bounds; VC_ERR_STATE before vc_finalize:
+ * all decided before anything is launched. */
+int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* phixy, int64_t phixy_stride, const float* nu, int64_t nu_stride,
+                         const float* dnu, const float* shape_inv, const float* loggamma, int64_t loggamma_stride, const float* logbeta,
+                         int64_t logbeta_stride, const float* nuomega, int64_t nuomega_stride, int64_t cell_begin, int64_t cell_count,
+                         double* gene_out_dev, double* cell_out_dev, float* dense_lppd_dev, void* hip_stream);
 
 /* introspection ----------------------------------------------------------------------------- */
 /* Copies the value a site took in the last vc_elbo_grad to host memory (synchronises the stream). */

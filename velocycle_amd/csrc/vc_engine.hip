@@ -136,6 +136,11 @@ struct vc_engine {
       kind = 0; dense = nullptr; indptr = nullptr; indices = nullptr; data = nullptr; nnz = 0;
     }
   } src[2];
+  // vc_pointwise_density (allocated at its first call): the histogram values sorted within every gene, their lgamma constants, the
+  // per-gene partial rows of one launch
+  float* pw_val = nullptr;
+  double* pw_lgc = nullptr;
+  double* pw_ws = nullptr;
   // what the last vc_finalize measured about its own set-up
   std::vector<int> h_ptr_host;          // the histogram CSR as uploaded (vc_get_histogram)
   std::vector<float> h_val_host, h_cnt_host;
@@ -1979,6 +1984,80 @@ extern "C" int vc_expected_logs(vc_engine* e, const float* nu, const float* dnu,
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return e->fail(VC_ERR_HIP, "vc_expected_logs: %s", hipGetErrorString(err));
   return VC_OK;
+}
+
+// workgroups (64 cells each) per launch of vc_pointwise_density: bounds its only workspace, [PW_MAX_SUPER][3 nmat][Ng] doubles
+static const int PW_MAX_SUPER = 512;
+
+extern "C" int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* phixy, int64_t phixy_stride, const float* nu,
+                                    int64_t nu_stride, const float* dnu, const float* shape_inv, const float* loggamma,
+                                    int64_t loggamma_stride, const float* logbeta, int64_t logbeta_stride, const float* nuomega,
+                                    int64_t nuomega_stride, int64_t cell_begin, int64_t cell_count, double* gene_out_dev,
+                                    double* cell_out_dev, float* dense_lppd_dev, void* hip_stream) {
+  if (!e) { vc_set_global_error("vc_pointwise_density: null engine"); return VC_ERR_ARG; }
+  VC_GUARD_BEGIN
+  if (n_draws < 2) return e->fail(VC_ERR_ARG, "vc_pointwise_density: n_draws must be >= 2 (the variance over draws divides by n_draws - 1)");
+  if (n_draws > (1 << 20)) return e->fail(VC_ERR_ARG, "vc_pointwise_density: more than 2^20 draws");
+  if (!gene_out_dev || !cell_out_dev) return e->fail(VC_ERR_ARG, "vc_pointwise_density: null gene_out_dev / cell_out_dev");
+  if (!e->finalized) return e->fail(VC_ERR_STATE, "vc_pointwise_density before vc_finalize");
+  const VcDims& d = e->d;
+  const VcBufs& b = e->b;
+  if (d.noise == VC_NOISE_LOGNORMAL)
+    return e->fail(VC_ERR_UNSUPPORTED, "vc_pointwise_density: Lognormal noise is not supported (NegativeBinomial or Poisson)");
+  if (d.generic || d.H < 1 || d.H > VC_MAXH || d.Hw > VC_MAXH)
+    return e->fail(VC_ERR_UNSUPPORTED, "vc_pointwise_density: this engine runs the run-time-sized kernel set (H = %d, Hw = %d, Nb = %d, LRMN rank %d, "
+                   "%d angular-speed coefficients): only what the compiled fast set covers is supported", d.H, d.Hw, d.Nb, d.R, d.NW);
+  const bool vel = d.model == VC_MODEL_VELOCITY, nb = d.noise == VC_NOISE_NB;
+  const int nbat = d.with_dnu ? d.Nb : 0;
+  if (!phixy || !nu) return e->fail(VC_ERR_ARG, "vc_pointwise_density: null phixy / nu");
+  if (nbat > 0 && !dnu) return e->fail(VC_ERR_ARG, "vc_pointwise_density: the model has batch offsets, dnu is required");
+  if (nb && !shape_inv) return e->fail(VC_ERR_ARG, "vc_pointwise_density: the negative binomial needs shape_inv");
+  if (vel && (!loggamma || !logbeta || !nuomega)) return e->fail(VC_ERR_ARG, "vc_pointwise_density: null loggamma / logbeta / nuomega");
+  if (vel && !b.U) return e->fail(VC_ERR_STATE, "vc_pointwise_density: the engine holds no unspliced counts");
+  auto stride_ok = [](int64_t s, long long full) { return s == 0 || s == full; };
+  if (!stride_ok(phixy_stride, 2LL * d.Nc) || !stride_ok(nu_stride, (long long)d.Ng * d.Nh) ||
+      (vel && (!stride_ok(loggamma_stride, d.Ng) || !stride_ok(logbeta_stride, d.Ng) || !stride_ok(nuomega_stride, d.NW))))
+    return e->fail(VC_ERR_ARG, "vc_pointwise_density: a draw stride must be 0 or the length of its site");
+  if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > d.Nc || (cell_begin & 63))
+    return e->fail(VC_ERR_ARG, "vc_pointwise_density: cells [%lld, %lld) must lie in [0, %d) and start at a multiple of 64",
+                   (long long)cell_begin, (long long)(cell_begin + cell_count), d.Nc);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int nmat = vel ? 2 : 1, NQ = 3 * nmat;
+  const int n_entries = (int)e->h_val_host.size();
+  if (!e->pw_ws) {
+    // the histogram values in ascending order within every gene (the dense bins come first, then the overflow list: ascending
+    // each, not together when a matrix holds non-integer counts)
+    std::vector<float> sorted = e->h_val_host;
+    const std::vector<int>& ptr = e->h_ptr_host;
+    for (size_t j = 0; j + 1 < ptr.size(); ++j) std::sort(sorted.begin() + ptr[j], sorted.begin() + ptr[j + 1]);
+    TRY(e->dalloc(&e->pw_val, sorted.size()));
+    if (!sorted.empty()) HIPCHK(e, hipMemcpy(e->pw_val, sorted.data(), sorted.size() * sizeof(float), hipMemcpyHostToDevice));
+    TRY(e->dalloc(&e->pw_lgc, sorted.size()));
+    const size_t supers = (size_t)std::min<long long>(PW_MAX_SUPER, ((long long)d.Nc + 63) / 64);
+    TRY(e->dalloc(&e->pw_ws, supers * NQ * (size_t)d.Ng));
+  }
+  vc_launch_pw_const(n_entries, d.Ng, 2, b.h_ptr, e->pw_val, shape_inv, d.noise, e->pw_lgc, st);
+  VcPwArgs a{};
+  a.S = b.S; a.U = b.U; a.cf = b.cf; a.Dm = b.Dm; a.Dbm = b.Dbm; a.cell_pos = b.cell_pos;
+  a.h_ptr = b.h_ptr; a.h_val = e->pw_val; a.h_lgc = e->pw_lgc;
+  a.phixy = phixy; a.nu = nu; a.dnu = dnu; a.shape_inv = shape_inv; a.loggamma = loggamma; a.logbeta = logbeta; a.nuomega = nuomega;
+  a.phixy_ds = phixy_stride; a.nu_ds = nu_stride; a.lg_ds = loggamma_stride; a.lb_ds = logbeta_stride; a.nw_ds = nuomega_stride;
+  a.n_draws = (int)n_draws; a.Ng = d.Ng; a.Nc = d.Nc; a.gbw = d.gbw; a.Nb = nbat; a.Nx = d.Nx; a.Hw = d.Hw; a.c16 = d.c16;
+  a.ws = e->pw_ws; a.cell_out = cell_out_dev; a.dense = dense_lppd_dev;
+  // everything eta_S depends on is the same in every draw: the S matrix is evaluated once
+  const int kind = !vel ? 0 : ((phixy_stride == 0 && nu_stride == 0) ? 2 : 1);
+  const long long c_end = cell_begin + cell_count;
+  for (long long c0 = cell_begin; c0 < c_end; c0 += 64LL * PW_MAX_SUPER) {
+    a.c_begin = (int)c0;
+    a.c_end = (int)std::min<long long>(c_end, c0 + 64LL * PW_MAX_SUPER);
+    const int n_super = (a.c_end - a.c_begin + 63) / 64;
+    if (vc_launch_pointwise(a, d.H, kind, d.noise, n_super, gene_out_dev, st) != VC_OK)
+      return e->fail(VC_ERR_UNSUPPORTED, "vc_pointwise_density: no kernel for H = %d", d.H);
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return e->fail(VC_ERR_HIP, "vc_pointwise_density: %s", hipGetErrorString(err));
+  return VC_OK;
+  VC_GUARD_END(e)
 }
 
 extern "C" int vc_read_site(vc_engine* e, int site, float* host_out, int64_t n, void* hip_stream) {

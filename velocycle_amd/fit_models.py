@@ -379,6 +379,50 @@ class _FitBase:
         the model; returns {site: (n, ...) CPU tensor} with Pyro's site shapes."""
         return {k: v.cpu() for k, v in self._draw_sites(num_samples, rs).items()}
 
+    def predictive_density(self, num_samples=None, seed=None, draws=None, return_pointwise=False):
+        """Pointwise predictive density of the fitted model over posterior draws (not in the reference): lppd, its WAIC penalty and
+        their sums per gene and per cell, as a `velocycle_amd.predictive.PredictiveDensity`.  num_samples (default: the model's
+        `num_samples`) guide draws are made on the device (Philox key `seed`; default: drawn from torch's generator) and stay there;
+        `draws` = explicit site draws instead ({site: (D, *site shape)}, per-cell sites for THIS rank's cells).  Cells sharded over
+        ranks: every rank evaluates its cells, per-cell results are gathered, per-gene results added in rank order."""
+        from . import predictive as P
+        if self.engine is None or getattr(self, "losses", None) is None:
+            raise ValueError("predictive_density: the model has not been fitted (call fit() first)")
+        sp = self.spec
+        n = int(self.num_samples if num_samples is None else num_samples) if draws is None else P._draw_count(draws)
+        nmat = 2 if sp.kind == "velocity" else 1
+        P.check_request(sp.noisemodel, n, sp.Ng, self.engine.Nc_local, nmat, return_pointwise)
+        eng = self.engine
+        if draws is None:
+            base = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if seed is None else int(seed)
+            base = broadcast_int(base, self._pg, eng.device)
+            names = [k for k in ("ν", "Δν", "ϕxy", "shape_inv", "logγg", "logβg", "νω") if self._site_exists(k)]
+            draws = eng.sample_posterior(names, n, seed=base, step0=0)
+        rec = P.pointwise_density(eng, draws, return_pointwise=return_pointwise)
+        if self._world == 1:
+            return rec
+        # every rank's record on every rank (per-cell blocks and per-gene rows gathered in rank order), merged by the one merge
+        # there is: predictive.merge_shards
+        # (the record holds CPU tensors; a collective of an RCCL-only group takes device tensors, like every other gather of this class)
+        mats, Q, dev = list(rec.lppd_cell), P.QUANTITIES, eng.device
+        cells = self._gather(torch.stack([getattr(rec, f + "_cell")[m] for f in Q for m in mats]).to(dev), 1)
+        genes = self._gather_ranks(torch.stack([getattr(rec, f + "_gene")[m] for f in Q for m in mats]))
+        pw = {m: self._gather(rec.pointwise[m].to(dev), 1) for m in mats} if rec.pointwise is not None else None
+        parts, c0 = [], 0
+        for r, nc_r in enumerate(self._shard_sizes):
+            pick = lambda src, j: {m: src[j * len(mats) + i].clone() for i, m in enumerate(mats)}
+            cr = cells[:, c0:c0 + nc_r]
+            parts.append(P.PredictiveDensity(lppd_gene=pick(genes[r], 0), lppd_cell=pick(cr, 0), mean_gene=pick(genes[r], 1),
+                                             mean_cell=pick(cr, 1), p_waic_gene=pick(genes[r], 2), p_waic_cell=pick(cr, 2),
+                                             n_draws=rec.n_draws,
+                                             pointwise=None if pw is None else {m: pw[m][:, c0:c0 + nc_r] for m in mats}))
+            c0 += nc_r
+        return P.merge_shards(parts)
+
+    def _gather_ranks(self, local: torch.Tensor) -> torch.Tensor:
+        """(world, *local.shape): every rank's copy of a replicated-shape tensor, in rank order."""
+        return gather_cells(local.unsqueeze(0).to(self.engine.device), 0, [1] * self._world, self._pg)
+
     def _site_exists(self, n):
         sp = self.spec
         return {"ν": True, "ϕxy": True, "Δν": sp.with_delta_nu, "shape_inv": sp.noisemodel == "NegativeBinomial",
