@@ -37,6 +37,11 @@
  *                               and its arg-max per cell (:508); stand-alone, no engine
  *   vc_pointwise_density        no counterpart (Predictive + a traced model run per draw would be it): lppd / WAIC of every
  *                               observed count over posterior draws, summed per gene and per cell
+ *   vc_sample_counts            the samplers behind pyro.sample("S" | "U", Poisson(mu) | GammaPoisson(1 / si, 1 / (si mu)))
+ *                               (velocity_inference_model.py:385-386, phase_inference_model.py:343-395); stand-alone, no engine
+ *   vc_predictive_check         Predictive(model, guide=guide, num_samples=n) with the observations removed
+ *                               (the call pattern of velocity_inference_model.py:189-291 on the model of :338-386): replicated
+ *                               counts per draw, reduced to statistics per gene and per cell
  */
 #ifndef VELOCYCLE_HIP_H
 #define VELOCYCLE_HIP_H
@@ -59,6 +64,7 @@ extern "C" {
 #define VC_ERR_UNSUPPORTED (-3)  /* configuration outside the compiled kernel set */
 #define VC_ERR_STATE (-4)        /* call order violated (e.g. step before finalize) */
 #define VC_ERR_NONFINITE (-5)    /* a step produced a NaN / Inf loss (vc_get_status) */
+#define VC_ERR_RANGE (-6)        /* the count sampler met a rate outside its range (vc_sample_counts, vc_predictive_check) */
 
 /* model / guide / noise selectors */
 #define VC_MODEL_PHASE 0         /* phase_latent_variable_model */
@@ -514,6 +520,45 @@ int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* phixy, int6
                          const float* dnu, const float* shape_inv, const float* loggamma, int64_t loggamma_stride, const float* logbeta,
                          int64_t logbeta_stride, const float* nuomega, int64_t nuomega_stride, int64_t cell_begin, int64_t cell_count,
                          double* gene_out_dev, double* cell_out_dev, float* dense_lppd_dev, void* hip_stream);
+
+/* --- device count sampler (stand-alone: no engine handle) ------------------------------------------------------------------
+ * k ~ Poisson(mu) (shape_inv_dev == NULL) or k ~ GammaPoisson(r, r / mu), r = 1 / shape_inv (the reference's negative binomial,
+ * velocity_inference_model.py:385-386, phase_inference_model.py), mu = exp(eta), for every element of eta_dev[n_rows][n_cols]
+ * (float32, natural log); shape_inv_dev holds one value per ROW.  Exact algorithms (no normal approximation): Marsaglia-Tsang gamma
+ * on polar normals with the u^(1/r) boost below r = 1, inversion by sequential search below a rate of 10, Hoermann's PTRS from there
+ * on.  Counter based: the count of element (i, j) is a pure function of
+ *   (seed, draw, matrix, index_origin + i * row_index_stride + j, eta, shape_inv)
+ * through Philox4x32-10 blocks (counter: index low, index high, draw, matrix << 16 | stage << 8 | attempt; key: seed), whatever the
+ * launch shape or the cutting into calls.  vc_predictive_check draws element (gene g, global cell c) of count matrix m under draw d
+ * at index g << 32 | c, matrix m, draw d.  Supported range: rates (after the gamma mixing) in [0, 2^20], shape_inv > 0.  An element
+ * outside it, or a rejection loop out of its 64 attempts, is stored as -1 and the call returns VC_ERR_RANGE: no value is made up.
+ * out_dev: int32[n_rows][n_cols].  draw in [0, 2^32), matrix in [0, 65536).  Synchronises hip_stream.  Errors: vc_last_error(NULL). */
+int vc_sample_counts(const float* eta_dev, int64_t n_rows, int64_t n_cols, const float* shape_inv_dev, uint64_t seed, int64_t draw,
+                     int matrix, int64_t index_origin, int64_t row_index_stride, int32_t* out_dev, void* hip_stream);
+
+/* --- posterior predictive check: replicated counts over posterior draws, reduced to statistics ------------------------------
+ * On the reference's stack: Predictive with the observations removed and [D][Ng][Nc] count tensors per matrix
+ * (velocity_inference_model.py:338-386, phase_inference_model.py:343-395 define the likelihood).  For draw d, count matrix m (S;
+ * velocity: S then U), gene g, cell c the replicate k_rep ~ the model's likelihood at eta_S / eta_U of vc_pointwise_density, drawn
+ * by the sampler of vc_sample_counts at index g << 32 | (cell_offset + c).  Draw pointers and strides as vc_pointwise_density.
+ * The call covers cells [cell_begin, cell_begin + cell_count) and draws [draw_begin, draw_begin + draw_count) of n_draws.  Outputs (DEVICE):
+ *   gene_rep_dev int64[n_draws][nmat][4][Ng]    sum k, sum k^2, #{k = 0}, max k over the call's cells, ADDED (max: maxed) into what the
+ *                                               buffer holds: zero it before the first call
+ *   cell_rep_dev int64[n_draws][nmat][Nc_local] sum k over the genes (the replicated library size), written for the call's cells and draws
+ *   gene_obs_dev double[nmat][4][Ng], cell_obs_dev double[nmat][Nc_local]: the same statistics of the engine's stored counts over the
+ *                                               call's cells (gene rows continued from what the buffer holds); both NULL: skipped (hand
+ *                                               them over with ONE of the draw ranges a set of cells is visited with)
+ *   keep_dev     NULL, or int32[n_keep][nmat][Ng][Nc_local]: the replicates of the draws < n_keep
+ * Replicate statistics are integers accumulated with 64-bit integer atomics; the observed ones are float64 sums in a fixed order: all
+ * of them are bit-identical under any cutting of cells and draws into calls, uint16 or float32 count storage, interleaved batches and
+ * repetition.  No workspace.  Synchronises hip_stream.  VC_ERR_UNSUPPORTED for Lognormal noise and the run-time-sized configurations,
+ * VC_ERR_ARG / VC_ERR_STATE as vc_pointwise_density (n_draws >= 1 here), all before anything is launched; VC_ERR_RANGE when a replicate
+ * left the sampler's range: latched in the engine (vc_get_status reports it too) until vc_clear_status. */
+int vc_predictive_check(vc_engine* e, int64_t n_draws, const float* phixy, int64_t phixy_stride, const float* nu, int64_t nu_stride,
+                        const float* dnu, const float* shape_inv, const float* loggamma, int64_t loggamma_stride, const float* logbeta,
+                        int64_t logbeta_stride, const float* nuomega, int64_t nuomega_stride, uint64_t seed, int64_t cell_begin,
+                        int64_t cell_count, int64_t draw_begin, int64_t draw_count, int64_t* gene_rep_dev, int64_t* cell_rep_dev,
+                        double* gene_obs_dev, double* cell_obs_dev, int32_t* keep_dev, int64_t n_keep, void* hip_stream);
 
 /* introspection ----------------------------------------------------------------------------- */
 /* Copies the value a site took in the last vc_elbo_grad to host memory (synchronises the stream). */

@@ -17,7 +17,7 @@ VC_ABI_VERSION = 2
 VC_OK = 0
 VC_PHASE_A, VC_PHASE_B, VC_PHASE_AB = 1, 2, 3
 VC_OPT_CLIPPED_ADAM, VC_OPT_ADAM = 0, 1
-VC_ERR_ARG, VC_ERR_HIP, VC_ERR_UNSUPPORTED, VC_ERR_STATE, VC_ERR_NONFINITE = -1, -2, -3, -4, -5
+VC_ERR_ARG, VC_ERR_HIP, VC_ERR_UNSUPPORTED, VC_ERR_STATE, VC_ERR_NONFINITE, VC_ERR_RANGE = -1, -2, -3, -4, -5, -6
 MODEL = {"phase": 0, "velocity": 1}
 GUIDE = {"meanfield": 0, "lrmn": 1}
 NOISE = {"NegativeBinomial": 0, "Poisson": 1, "Lognormal": 2}
@@ -135,6 +135,12 @@ EXPORTS = {
     "vc_pointwise_density": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vc_sample_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int64, C.c_int64,
+                                   C.c_void_p, C.c_void_p]),
+    "vc_predictive_check": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint64, C.c_int64,
+                                      C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_void_p]),
     "vc_read_site": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "vc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(vc_stats)]),
     "vc_get_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
@@ -149,6 +155,10 @@ _lib = None
 
 class HipLibraryError(RuntimeError):
     pass
+
+
+class CountSamplerRangeError(RuntimeError):
+    """VC_ERR_RANGE: the device count sampler met a rate outside its supported range (vc_sample_counts, vc_predictive_check)."""
 
 
 def load():

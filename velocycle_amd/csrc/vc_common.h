@@ -1042,6 +1042,27 @@ struct VcPwArgs {
 int vc_launch_pointwise(const VcPwArgs& a, int H, int kind, int noise, int n_super, double* gene_out, hipStream_t st);
 void vc_launch_pw_const(int n_entries, int Ng, int nmat, const int* h_ptr, const float* h_val, const float* shape_inv, int noise,
                         double* out, hipStream_t st);
+// posterior predictive check (vc_ppc.hip): what one call's launches read and write
+struct VcPpcArgs {
+  const void *S, *U;                  // blocked counts as vc_finalize left them (c16: uint16, else float32): the observed statistics
+  const float *cf, *Dm, *Dbm;         // (Nc), (Nx, Nc), (Nb, Nc) in the caller's cell order
+  const int* cell_pos;                // position of cell c in the blocked counts, or nullptr: the identity
+  const float *phixy, *nu, *dnu, *shape_inv, *loggamma, *logbeta, *nuomega;      // the draws of every site (dnu, shape_inv: one value)
+  long long phixy_ds, nu_ds, lg_ds, lb_ds, nw_ds;                                // their draw strides in floats (0: the same in every draw)
+  uint64_t seed;                      // Philox key
+  long long cell_offset;              // global index of local cell 0 (the sampler's element index takes the GLOBAL cell)
+  int Ng, Nc, gbw, Nb, Nx, Hw, c16;
+  int c_begin, c_end;                 // cells [c_begin, c_end) of the call
+  int d_begin;                        // first draw of the launch (workgroup row y: draw d_begin + y)
+  int n_keep;                         // dense replicates are stored for the draws < n_keep
+  unsigned long long* gene_rep;       // [D][nmat][4][Ng]  sum k, sum k^2, #{k = 0}, max k over the cells: integer atomics
+  unsigned long long* cell_rep;       // [D][nmat][Nc]     sum k over the genes
+  double *gene_obs, *cell_obs;        // [nmat][4][Ng], [nmat][Nc]: the same of the observed counts, or nullptr
+  int* keep;                          // [n_keep][nmat][Ng][Nc] or nullptr
+  unsigned long long* status;         // the engine's latch of sampler failures (status[3])
+};
+int vc_launch_ppc(const VcPpcArgs& a, int H, bool vel, bool nb, int d_end, hipStream_t st);
+void vc_launch_ppc_observed(const VcPpcArgs& a, int nmat, hipStream_t st);
 void vc_launch_pre(const VcDims& d, const VcBufs& b, const float* params, const float* eps,
                    uint64_t seed, long long step, const long long* step_dev, int cond_only, int with_hist,
                    hipStream_t st, int particles = 1, int particle = 0);

@@ -1245,7 +1245,8 @@ static int fin_step_buffers(vc_engine* e) {
   b.step_ctr = nullptr;
   TRY(e->dalloc(&b.step_size, 2));
   HIPCHK(e, hipMemset(b.step_size, 0, 2 * sizeof(float)));
-  TRY(e->dalloc(&b.status, 4));       // [0] steps with a non-finite loss, [1] 1 + the first of them, [2] 1 + step of an exchange time-out
+  TRY(e->dalloc(&b.status, 4));       // [0] steps with a non-finite loss, [1] 1 + the first of them, [2] 1 + step of an exchange time-out,
+                                      // [3] replicates the count sampler refused (vc_predictive_check)
   HIPCHK(e, hipMemset(b.status, 0, 4 * sizeof(long long)));
   return VC_OK;
 }
@@ -2060,6 +2061,72 @@ extern "C" int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* 
   VC_GUARD_END(e)
 }
 
+extern "C" int vc_predictive_check(vc_engine* e, int64_t n_draws, const float* phixy, int64_t phixy_stride, const float* nu,
+                                   int64_t nu_stride, const float* dnu, const float* shape_inv, const float* loggamma,
+                                   int64_t loggamma_stride, const float* logbeta, int64_t logbeta_stride, const float* nuomega,
+                                   int64_t nuomega_stride, uint64_t seed, int64_t cell_begin, int64_t cell_count, int64_t draw_begin,
+                                   int64_t draw_count, int64_t* gene_rep_dev, int64_t* cell_rep_dev, double* gene_obs_dev,
+                                   double* cell_obs_dev, int32_t* keep_dev, int64_t n_keep, void* hip_stream) {
+  if (!e) { vc_set_global_error("vc_predictive_check: null engine"); return VC_ERR_ARG; }
+  if (n_draws < 1) return e->fail(VC_ERR_ARG, "vc_predictive_check: n_draws must be >= 1");
+  if (n_draws > (1 << 20)) return e->fail(VC_ERR_ARG, "vc_predictive_check: more than 2^20 draws");
+  if (!gene_rep_dev || !cell_rep_dev) return e->fail(VC_ERR_ARG, "vc_predictive_check: null gene_rep_dev / cell_rep_dev");
+  if ((gene_obs_dev != nullptr) != (cell_obs_dev != nullptr))
+    return e->fail(VC_ERR_ARG, "vc_predictive_check: gene_obs_dev and cell_obs_dev are given together or not at all");
+  if (!e->finalized) return e->fail(VC_ERR_STATE, "vc_predictive_check before vc_finalize");
+  const VcDims& d = e->d;
+  const VcBufs& b = e->b;
+  if (d.noise == VC_NOISE_LOGNORMAL)
+    return e->fail(VC_ERR_UNSUPPORTED, "vc_predictive_check: Lognormal noise is not supported (NegativeBinomial or Poisson)");
+  if (d.generic || d.H < 1 || d.H > VC_MAXH || d.Hw > VC_MAXH)
+    return e->fail(VC_ERR_UNSUPPORTED, "vc_predictive_check: this engine runs the run-time-sized kernel set (H = %d, Hw = %d, Nb = %d, LRMN rank %d, "
+                   "%d angular-speed coefficients): only what the compiled fast set covers is supported", d.H, d.Hw, d.Nb, d.R, d.NW);
+  const bool vel = d.model == VC_MODEL_VELOCITY, nb = d.noise == VC_NOISE_NB;
+  const int nbat = d.with_dnu ? d.Nb : 0;
+  if (!phixy || !nu) return e->fail(VC_ERR_ARG, "vc_predictive_check: null phixy / nu");
+  if (nbat > 0 && !dnu) return e->fail(VC_ERR_ARG, "vc_predictive_check: the model has batch offsets, dnu is required");
+  if (nb && !shape_inv) return e->fail(VC_ERR_ARG, "vc_predictive_check: the negative binomial needs shape_inv");
+  if (vel && (!loggamma || !logbeta || !nuomega)) return e->fail(VC_ERR_ARG, "vc_predictive_check: null loggamma / logbeta / nuomega");
+  if (vel && gene_obs_dev && !b.U) return e->fail(VC_ERR_STATE, "vc_predictive_check: the engine holds no unspliced counts");
+  auto stride_ok = [](int64_t s, long long full) { return s == 0 || s == full; };
+  if (!stride_ok(phixy_stride, 2LL * d.Nc) || !stride_ok(nu_stride, (long long)d.Ng * d.Nh) ||
+      (vel && (!stride_ok(loggamma_stride, d.Ng) || !stride_ok(logbeta_stride, d.Ng) || !stride_ok(nuomega_stride, d.NW))))
+    return e->fail(VC_ERR_ARG, "vc_predictive_check: a draw stride must be 0 or the length of its site");
+  if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > d.Nc)
+    return e->fail(VC_ERR_ARG, "vc_predictive_check: cells [%lld, %lld) must lie in [0, %d)", (long long)cell_begin,
+                   (long long)(cell_begin + cell_count), d.Nc);
+  if (draw_begin < 0 || draw_count < 1 || draw_begin + draw_count > n_draws)
+    return e->fail(VC_ERR_ARG, "vc_predictive_check: draws [%lld, %lld) must lie in [0, %lld)", (long long)draw_begin,
+                   (long long)(draw_begin + draw_count), (long long)n_draws);
+  if (n_keep < 0 || n_keep > n_draws || (n_keep > 0) != (keep_dev != nullptr))
+    return e->fail(VC_ERR_ARG, "vc_predictive_check: n_keep must lie in [0, n_draws] and come with keep_dev");
+  hipStream_t st = (hipStream_t)hip_stream;
+  VcPpcArgs a{};
+  a.S = b.S; a.U = b.U; a.cf = b.cf; a.Dm = b.Dm; a.Dbm = b.Dbm; a.cell_pos = b.cell_pos;
+  a.phixy = phixy; a.nu = nu; a.dnu = dnu; a.shape_inv = shape_inv; a.loggamma = loggamma; a.logbeta = logbeta; a.nuomega = nuomega;
+  a.phixy_ds = phixy_stride; a.nu_ds = nu_stride; a.lg_ds = loggamma_stride; a.lb_ds = logbeta_stride; a.nw_ds = nuomega_stride;
+  a.seed = seed; a.cell_offset = d.cell_offset;
+  a.Ng = d.Ng; a.Nc = d.Nc; a.gbw = d.gbw; a.Nb = nbat; a.Nx = d.Nx; a.Hw = d.Hw; a.c16 = d.c16;
+  a.c_begin = (int)cell_begin; a.c_end = (int)(cell_begin + cell_count); a.d_begin = (int)draw_begin; a.n_keep = (int)n_keep;
+  a.gene_rep = (unsigned long long*)gene_rep_dev; a.cell_rep = (unsigned long long*)cell_rep_dev;
+  a.gene_obs = gene_obs_dev; a.cell_obs = cell_obs_dev; a.keep = keep_dev;
+  a.status = (unsigned long long*)(b.status + 3);
+  if (gene_obs_dev) vc_launch_ppc_observed(a, vel ? 2 : 1, st);
+  if (vc_launch_ppc(a, d.H, vel, nb, (int)(draw_begin + draw_count), st) != VC_OK)
+    return e->fail(VC_ERR_UNSUPPORTED, "vc_predictive_check: no kernel for H = %d", d.H);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return e->fail(VC_ERR_HIP, "vc_predictive_check: %s", hipGetErrorString(err));
+  // the sampler's latch: the call fails by name when an element left the supported range (sticky until vc_clear_status)
+  long long bad = 0;
+  HIPCHK(e, hipStreamSynchronize(st));
+  HIPCHK(e, hipMemcpy(&bad, b.status + 3, sizeof bad, hipMemcpyDeviceToHost));
+  if (bad > 0)
+    return e->fail(VC_ERR_RANGE, "vc_predictive_check: %lld replicate(s) outside the count sampler's range (rate not finite or above 2^20, "
+                   "shape_inv <= 0, or a rejection loop out of attempts) since the last vc_clear_status; the tables of this call are not valid",
+                   bad);
+  return VC_OK;
+}
+
 extern "C" int vc_read_site(vc_engine* e, int site, float* host_out, int64_t n, void* hip_stream) {
   if (!e || !host_out) return VC_ERR_ARG;
   if (!e->finalized) return e->fail(VC_ERR_STATE, "vc_read_site before vc_finalize");
@@ -2131,6 +2198,8 @@ extern "C" int vc_get_status(vc_engine* e, int64_t* first_bad_step, int64_t* n_b
   if (n_bad) *n_bad = h[0];
   if (h[0] > 0)
     return e->fail(VC_ERR_NONFINITE, "non-finite loss in %lld step(s), first at step %lld", h[0], h[1] - 1);
+  if (h[3] > 0)
+    return e->fail(VC_ERR_RANGE, "%lld replicate(s) outside the count sampler's range (vc_predictive_check)", h[3]);
   return VC_OK;
 }
 

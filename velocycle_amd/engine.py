@@ -89,6 +89,8 @@ class HipEngine:
                 raise NotImplementedError(msg)
             if rc == _lib.VC_ERR_ARG:
                 raise ValueError(msg)
+            if rc == _lib.VC_ERR_RANGE:
+                raise _lib.CountSamplerRangeError(msg)
             raise HipEngineError(msg)
 
     def _stream(self):

@@ -419,6 +419,44 @@ class _FitBase:
             c0 += nc_r
         return P.merge_shards(parts)
 
+    def posterior_predictive_check(self, num_samples=None, seed=None, draws=None, keep_replicates=0):
+        """Posterior predictive check of the fitted model (on the reference's stack: Predictive with the observations removed): one
+        replicated count matrix per posterior draw, reduced on the device to statistics per gene and per cell, as a
+        `velocycle_amd.predictive.PredictiveCheck` (replicate mean / sd and p-values of mean, variance, zero fraction and max per
+        gene and of the library size per cell).  num_samples / seed / draws as `predictive_density`; `seed` also keys the count
+        sampler.  keep_replicates = n keeps the dense replicates of the first n draws.  Cells sharded over ranks: every rank
+        replicates its cells, the records are gathered and merged (`predictive.merge_check_shards`)."""
+        from . import predictive as P
+        if self.engine is None or getattr(self, "losses", None) is None:
+            raise ValueError("posterior_predictive_check: the model has not been fitted (call fit() first)")
+        sp = self.spec
+        n = int(self.num_samples if num_samples is None else num_samples) if draws is None else P._draw_count(draws)
+        nmat = 2 if sp.kind == "velocity" else 1
+        P.check_ppc_request(sp.noisemodel, n, sp.Ng, self.engine.Nc_local, nmat, keep_replicates)
+        eng = self.engine
+        base = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if seed is None else int(seed)
+        base = broadcast_int(base, self._pg, eng.device)
+        if draws is None:
+            names = [k for k in ("ν", "Δν", "ϕxy", "shape_inv", "logγg", "logβg", "νω") if self._site_exists(k)]
+            draws = eng.sample_posterior(names, n, seed=base, step0=0)
+        rec = P.predictive_check(eng, draws, seed=base, keep_replicates=keep_replicates)
+        if self._world == 1:
+            return rec
+        mats, dev = list(rec.cell_rep), eng.device
+        cell_rep = self._gather(torch.stack([rec.cell_rep[m] for m in mats]).to(dev), 2)
+        cell_obs = self._gather(torch.stack([rec.cell_obs[m] for m in mats]).to(dev), 1)
+        gene_rep = self._gather_ranks(torch.stack([rec.gene_rep[m] for m in mats]))
+        gene_obs = self._gather_ranks(torch.stack([rec.gene_obs[m] for m in mats]))
+        reps = self._gather(torch.stack([rec.replicates[m] for m in mats]).to(dev), 3) if rec.replicates is not None else None
+        parts, c0 = [], 0
+        for r, nc_r in enumerate(self._shard_sizes):
+            pick = lambda src: {m: src[i].clone() for i, m in enumerate(mats)}
+            parts.append(P.PredictiveCheck(gene_rep=pick(gene_rep[r]), cell_rep=pick(cell_rep[:, :, c0:c0 + nc_r]), gene_obs=pick(gene_obs[r]),
+                                           cell_obs=pick(cell_obs[:, c0:c0 + nc_r]), n_draws=rec.n_draws, n_cells=nc_r, seed=rec.seed,
+                                           replicates=None if reps is None else pick(reps[:, :, :, c0:c0 + nc_r])))
+            c0 += nc_r
+        return P.merge_check_shards(parts)
+
     def _gather_ranks(self, local: torch.Tensor) -> torch.Tensor:
         """(world, *local.shape): every rank's copy of a replicated-shape tensor, in rank order."""
         return gather_cells(local.unsqueeze(0).to(self.engine.device), 0, [1] * self._world, self._pg)

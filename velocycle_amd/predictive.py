@@ -81,26 +81,12 @@ def _draw_count(draws) -> int:
     return max(int(draws[k].shape[0]) for k in ("ν", "ϕxy", "logγg", "logβg", "νω") if k in draws)
 
 
-def pointwise_density(engine, draws: Dict[str, torch.Tensor], *, return_pointwise: bool = False,
-                      chunk_cells: Optional[int] = None) -> PredictiveDensity:
-    """lppd / mean / p_waic of this engine's cells under explicit draws.
-
-    draws: {site: (D, *site shape) tensor} as `HipEngine.sample_posterior` returns them ("ν", "ϕxy" and, where the model has them,
-    "Δν", "shape_inv", "logγg", "logβg", "νω"; other keys are ignored).  A site that is the same in every draw (conditioned, or one
-    of the guide's Delta sites) may be given with a leading dimension of 1: it then costs nothing per draw, and when everything the
-    spliced term depends on is such a site, the S matrix is evaluated once (its p_waic is exactly 0).  Draws given with the full leading
-    dimension are checked for that on the device.
-    chunk_cells: cells per library call (rounded up to a multiple of 64; default: all).  The result does not depend on it.
-    Results are for this engine's cells, in the caller's order."""
+def _device_draws(engine, draws, D):
+    """The sites of this engine's model out of `draws` as contiguous float32 device tensors: ({site: pointer}, {site: draw stride in
+    floats, 0 for a site that is the same in every draw}, the tensors to keep alive)."""
     sp = engine.spec
     vel = sp.kind == "velocity"
-    mats = ["S", "U"] if vel else ["S"]
-    D = _draw_count(draws)
     Ng, Nc = sp.Ng, engine.Nc_local
-    check_request(sp.noisemodel, D, Ng, Nc, len(mats), return_pointwise)
-    if engine.stats["generic"]:
-        raise NotImplementedError(f"pointwise_density: this engine runs the run-time-sized kernel set (H = {sp.H}, Hw = {sp.Hw}, Nb = {sp.Nb}): "
-                                  "only what the compiled fast set covers is supported")
     dev = engine.device
     nb = sp.noisemodel == "NegativeBinomial"
     need = {"ϕxy": (Nc, 2), "ν": (Ng, sp.Nh)}
@@ -133,6 +119,31 @@ def pointwise_density(engine, draws: Dict[str, torch.Tensor], *, return_pointwis
         keep.append(t)
         ptr[name] = C.c_void_p(t.data_ptr())
         stride[name] = 0 if t.shape[0] == 1 else n
+    return ptr, stride, keep
+
+
+def pointwise_density(engine, draws: Dict[str, torch.Tensor], *, return_pointwise: bool = False,
+                      chunk_cells: Optional[int] = None) -> PredictiveDensity:
+    """lppd / mean / p_waic of this engine's cells under explicit draws.
+
+    draws: {site: (D, *site shape) tensor} as `HipEngine.sample_posterior` returns them ("ν", "ϕxy" and, where the model has them,
+    "Δν", "shape_inv", "logγg", "logβg", "νω"; other keys are ignored).  A site that is the same in every draw (conditioned, or one
+    of the guide's Delta sites) may be given with a leading dimension of 1: it then costs nothing per draw, and when everything the
+    spliced term depends on is such a site, the S matrix is evaluated once (its p_waic is exactly 0).  Draws given with the full leading
+    dimension are checked for that on the device.
+    chunk_cells: cells per library call (rounded up to a multiple of 64; default: all).  The result does not depend on it.
+    Results are for this engine's cells, in the caller's order."""
+    sp = engine.spec
+    vel = sp.kind == "velocity"
+    mats = ["S", "U"] if vel else ["S"]
+    D = _draw_count(draws)
+    Ng, Nc = sp.Ng, engine.Nc_local
+    check_request(sp.noisemodel, D, Ng, Nc, len(mats), return_pointwise)
+    if engine.stats["generic"]:
+        raise NotImplementedError(f"pointwise_density: this engine runs the run-time-sized kernel set (H = {sp.H}, Hw = {sp.Hw}, Nb = {sp.Nb}): "
+                                  "only what the compiled fast set covers is supported")
+    dev = engine.device
+    ptr, stride, keep = _device_draws(engine, draws, D)
     nq = 3 * len(mats)
     gene = torch.zeros((nq, Ng), dtype=torch.float64, device=dev)
     cell = torch.zeros((nq, Nc), dtype=torch.float64, device=dev)
@@ -187,3 +198,185 @@ def compare(a: PredictiveDensity, b: PredictiveDensity):
     n = diff.numel()
     se = math.sqrt(n * float(diff.var(unbiased=True))) if n > 1 else float("nan")
     return float(diff.sum()), se
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# posterior predictive check: replicated counts over posterior draws (vc_predictive_check, csrc/vc_ppc.hip), the device count
+# sampler on its own (vc_sample_counts, csrc/vc_count_sampler.h)
+# ----------------------------------------------------------------------------------------------------------------------------------
+STATISTICS = ("mean", "variance", "zero_fraction", "max")
+SAMPLER_MU_MAX = float(1 << 20)      # supported range of the sampler's Poisson rate (VC_CS_MU_MAX)
+
+
+def _p_values(rep, obs, n):
+    ge = (rep >= obs).sum(0).double() / n
+    gt = (rep > obs).sum(0).double() / n
+    return {"p_ge": ge, "p_gt": gt, "p_mid": 0.5 * (ge + gt)}
+
+
+@dataclass
+class PredictiveCheck:
+    """Replicated-count statistics of a fit, per count matrix {"S": ..., "U": ...}, CPU tensors.
+
+    gene_rep[m]  (D, 4, Ng) int64: per draw and gene, over the record's cells: sum k, sum k^2, #{k = 0}, max k of the replicates
+    cell_rep[m]  (D, Nc) int64: per draw and cell, sum k over the genes (the replicated library size)
+    gene_obs[m]  (4, Ng) float64, cell_obs[m] (Nc,) float64: the same statistics of the observed counts
+    replicates[m] (n_keep, Ng, Nc) int32 of the first n_keep draws, when asked for.
+    Derived (float64, formed on the host): `gene_T_rep` (D, 4, Ng) / `gene_T_obs` (4, Ng) with T in STATISTICS order (the variance is
+    sum k^2 / n - mean^2), and `gene(stat)` / `library_size()`: replicate mean and sd over draws, p_ge = #{d: T_rep >= T_obs} / D,
+    p_gt, p_mid = (p_ge + p_gt) / 2."""
+    gene_rep: Dict[str, torch.Tensor]
+    cell_rep: Dict[str, torch.Tensor]
+    gene_obs: Dict[str, torch.Tensor]
+    cell_obs: Dict[str, torch.Tensor]
+    n_draws: int
+    n_cells: int
+    seed: int
+    replicates: Optional[Dict[str, torch.Tensor]] = None
+
+    @staticmethod
+    def _T(tab, n):
+        t = tab.double()
+        mean = t[..., 0, :] / n
+        return torch.stack([mean, t[..., 1, :] / n - mean * mean, t[..., 2, :] / n, t[..., 3, :]], dim=-2)
+
+    @property
+    def gene_T_rep(self):
+        return {m: self._T(v, self.n_cells) for m, v in self.gene_rep.items()}
+
+    @property
+    def gene_T_obs(self):
+        return {m: self._T(v, self.n_cells) for m, v in self.gene_obs.items()}
+
+    @staticmethod
+    def _summary(rep, obs, n):
+        out = {"obs": obs, "rep_mean": rep.mean(0), "rep_sd": rep.std(0, unbiased=True) if n > 1 else torch.zeros_like(obs)}
+        out.update(_p_values(rep, obs, n))
+        return out
+
+    def gene(self, stat: str):
+        """{matrix: {"obs", "rep_mean", "rep_sd", "p_ge", "p_gt", "p_mid"}: (Ng,) float64} of one of STATISTICS."""
+        j = STATISTICS.index(stat)
+        rep, obs = self.gene_T_rep, self.gene_T_obs
+        return {m: self._summary(rep[m][:, j], obs[m][j], self.n_draws) for m in rep}
+
+    def library_size(self):
+        """{matrix: {...}: (Nc,) float64}: the same summary of the per-cell sum over genes."""
+        return {m: self._summary(self.cell_rep[m].double(), self.cell_obs[m], self.n_draws) for m in self.cell_rep}
+
+
+def check_ppc_request(noisemodel: str, n_draws: int, Ng: int, Nc: int, n_matrices: int, keep_replicates: int):
+    """The refusals of predictive_check that need no device: raised before any library or GPU call."""
+    if noisemodel == "Lognormal":
+        raise NotImplementedError("predictive_check: Lognormal noise is not supported (NegativeBinomial or Poisson)")
+    if noisemodel not in ("NegativeBinomial", "Poisson"):
+        raise ValueError(f"{noisemodel} not allowed")
+    if int(n_draws) < 1:
+        raise ValueError(f"predictive_check needs at least 1 draw, got {n_draws}")
+    if not 0 <= int(keep_replicates) <= int(n_draws):
+        raise ValueError(f"keep_replicates must lie in [0, {n_draws}], got {keep_replicates}")
+    if 4 * int(keep_replicates) * int(Ng) * int(Nc) * int(n_matrices) > MAX_POINTWISE_BYTES:
+        raise ValueError(f"keep_replicates: the dense replicates of {keep_replicates} x {n_matrices} x {Ng} x {Nc} elements exceed "
+                         f"{MAX_POINTWISE_BYTES} bytes; use the per-draw statistics")
+
+
+def predictive_check(engine, draws: Dict[str, torch.Tensor], *, seed: int, keep_replicates: int = 0,
+                     chunk_cells: Optional[int] = None, chunk_draws: Optional[int] = None) -> PredictiveCheck:
+    """Replicated counts of this engine's cells under explicit draws (as `pointwise_density` takes them), reduced on the device to
+    per-draw statistics; nothing of size D x Ng x Nc exists unless keep_replicates asks for the first draws' replicates.
+    seed: Philox key of the count sampler; a replicate depends on (seed, draw, matrix, gene, global cell) and its latents alone.
+    chunk_cells / chunk_draws: cells / draws per library call (default: all); the result does not depend on them."""
+    sp = engine.spec
+    vel = sp.kind == "velocity"
+    mats = ["S", "U"] if vel else ["S"]
+    D = _draw_count(draws)
+    Ng, Nc = sp.Ng, engine.Nc_local
+    n_keep = int(keep_replicates)
+    check_ppc_request(sp.noisemodel, D, Ng, Nc, len(mats), n_keep)
+    if engine.stats["generic"]:
+        raise NotImplementedError(f"predictive_check: this engine runs the run-time-sized kernel set (H = {sp.H}, Hw = {sp.Hw}, Nb = {sp.Nb}): "
+                                  "only what the compiled fast set covers is supported")
+    dev = engine.device
+    ptr, stride, keep = _device_draws(engine, draws, D)
+    nm = len(mats)
+    gene_rep = torch.zeros((D, nm, 4, Ng), dtype=torch.int64, device=dev)
+    cell_rep = torch.zeros((D, nm, Nc), dtype=torch.int64, device=dev)
+    gene_obs = torch.zeros((nm, 4, Ng), dtype=torch.float64, device=dev)
+    cell_obs = torch.zeros((nm, Nc), dtype=torch.float64, device=dev)
+    dense = torch.zeros((n_keep, nm, Ng, Nc), dtype=torch.int32, device=dev) if n_keep else None
+    cstep = Nc if not chunk_cells else max(1, int(chunk_cells))
+    dstep = D if not chunk_draws else max(1, int(chunk_draws))
+    g = lambda k: ptr.get(k)
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    for c0 in range(0, Nc, cstep):
+        for d0 in range(0, D, dstep):
+            first = d0 == 0                               # the observed statistics of a set of cells are formed once
+            engine._check(engine.lib.vc_predictive_check(
+                engine._h, C.c_int64(D), g("ϕxy"), C.c_int64(stride["ϕxy"]), g("ν"), C.c_int64(stride["ν"]), g("Δν"), g("shape_inv"),
+                g("logγg"), C.c_int64(stride.get("logγg", 0)), g("logβg"), C.c_int64(stride.get("logβg", 0)), g("νω"),
+                C.c_int64(stride.get("νω", 0)), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_int64(c0), C.c_int64(min(cstep, Nc - c0)),
+                C.c_int64(d0), C.c_int64(min(dstep, D - d0)), vp(gene_rep), vp(cell_rep), vp(gene_obs) if first else None,
+                vp(cell_obs) if first else None, vp(dense), C.c_int64(n_keep), engine._stream()))
+    torch.cuda.synchronize(dev)
+    del keep
+    pick = lambda t, ax: {m: t.select(ax, i).cpu().clone() for i, m in enumerate(mats)}
+    return PredictiveCheck(gene_rep=pick(gene_rep, 1), cell_rep=pick(cell_rep, 1), gene_obs=pick(gene_obs, 0), cell_obs=pick(cell_obs, 0),
+                           n_draws=D, n_cells=Nc, seed=int(seed), replicates=None if dense is None else pick(dense, 1))
+
+
+def merge_check_shards(parts) -> PredictiveCheck:
+    """The records of the ranks of a cell-sharded check, in rank order, as one record: per-gene sums added, the max taken as max,
+    per-cell tables (and kept replicates) concatenated.  Integer tables merge exactly; the observed sums are added in rank order."""
+    parts = list(parts)
+    first = parts[0]
+    if any(p.n_draws != first.n_draws or p.seed != first.seed for p in parts):
+        raise ValueError("merge_check_shards: the records come from different draws or seeds")
+
+    def genes(f):
+        out = {}
+        for m in getattr(first, f):
+            acc = getattr(first, f)[m].clone()
+            for p in parts[1:]:
+                t = getattr(p, f)[m]
+                acc[..., :3, :] = acc[..., :3, :] + t[..., :3, :]
+                acc[..., 3, :] = torch.maximum(acc[..., 3, :], t[..., 3, :])
+            out[m] = acc
+        return out
+    cat = lambda f, dim: {m: torch.cat([getattr(p, f)[m] for p in parts], dim=dim) for m in getattr(first, f)}
+    reps = None if first.replicates is None else cat("replicates", 2)
+    return PredictiveCheck(gene_rep=genes("gene_rep"), cell_rep=cat("cell_rep", 1), gene_obs=genes("gene_obs"), cell_obs=cat("cell_obs", 0),
+                           n_draws=first.n_draws, n_cells=sum(p.n_cells for p in parts), seed=first.seed, replicates=reps)
+
+
+def sample_counts(eta: torch.Tensor, shape_inv: Optional[torch.Tensor] = None, *, seed: int, draw: int = 0, matrix: int = 0,
+                  index_origin: int = 0, row_index_stride: Optional[int] = None) -> torch.Tensor:
+    """Counts k ~ Poisson(exp(eta)) (shape_inv None) or GammaPoisson(1 / shape_inv, 1 / (shape_inv exp(eta))) on the device: int32
+    tensor of eta's shape (vc_sample_counts).  eta: float32 DEVICE tensor, natural-log means, 1-D or (rows, columns); shape_inv: one
+    value per row.  Element (i, j) is a pure function of (seed, draw, matrix, index_origin + i * row_index_stride + j, eta, shape_inv);
+    row_index_stride defaults to the number of columns.  Exact samplers, rates up to 2^20 (`SAMPLER_MU_MAX`): an element beyond it
+    raises `CountSamplerRangeError`.  There is no CPU path."""
+    from . import _lib
+    if not eta.is_cuda:
+        raise ValueError("sample_counts: eta must be a device tensor (there is no CPU path)")
+    if eta.dim() not in (1, 2) or eta.numel() == 0:
+        raise ValueError(f"sample_counts: eta must be a non-empty 1-D or 2-D tensor, got shape {tuple(eta.shape)}")
+    e = eta.to(torch.float32).contiguous()
+    rows, cols = (1, e.shape[0]) if e.dim() == 1 else (e.shape[0], e.shape[1])
+    si = None
+    if shape_inv is not None:
+        si = torch.as_tensor(shape_inv, dtype=torch.float32).to(e.device).reshape(-1).contiguous()
+        if si.numel() != rows:
+            raise ValueError(f"sample_counts: shape_inv holds {si.numel()} values for {rows} row(s)")
+    lib = _lib.load()
+    out = torch.empty(e.shape, dtype=torch.int32, device=e.device)
+    with torch.cuda.device(e.device):
+        rc = lib.vc_sample_counts(C.c_void_p(e.data_ptr()), C.c_int64(rows), C.c_int64(cols), C.c_void_p(si.data_ptr()) if si is not None else None,
+                                  C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_int64(int(draw)), C.c_int(int(matrix)), C.c_int64(int(index_origin)),
+                                  C.c_int64(cols if row_index_stride is None else int(row_index_stride)), C.c_void_p(out.data_ptr()),
+                                  C.c_void_p(torch.cuda.current_stream(e.device).cuda_stream))
+    if rc != _lib.VC_OK:
+        msg = lib.vc_last_error(None).decode()
+        if rc == _lib.VC_ERR_RANGE:
+            raise _lib.CountSamplerRangeError(msg)
+        raise (ValueError if rc == _lib.VC_ERR_ARG else RuntimeError)(msg)
+    return out
