@@ -3,10 +3,15 @@ csrc/vc_ppc.hip): a numpy restatement of Philox4x32-10 and of the documented cou
 fixture's draws, and the statistics / p-values of replicated counts.
 
 The arithmetic dtype of the sampler is a parameter: float64 is the checker, float32 "the reference's own error" -- the same operations
-in the same order with one float32 rounding each, which is what the device performs (its exp2 / log2 are the hardware's).  Where a
+in the same order with one float32 rounding each, which is what the device performs (its exp2 / log2 are the hardware's).  PTRS's full
+acceptance test is float64 under either dtype, from the inputs the dtype produced, as on the device.  Where a
 float32 evaluation lands on the other side of an accept / floor / search decision than the float64 one, the count differs: the share
 of such elements between the two restatements, times SAFETY, caps the share the device may differ from the float64 checker by.
+
+Against the exact pmf of torch.distributions (nothing shared with the sampler): exact_moments / moment_z and the chi-square gof_z, over
+GRID (rates up to 400) and LARGE_GRID (rates up to the documented 2^20).
 """
+from functools import lru_cache
 import math
 
 import numpy as np
@@ -59,18 +64,20 @@ def _ln(x, dt):
     return _consts(dt)[0] * np.log2(x)
 
 
-def lfact(k, dt):
+def lfact(k):
+    """log(k!) of vc_cs_lfact: float64, whatever the dtype of the rest."""
+    dt = np.float64
     x = k + dt(1)
     small = x < dt(8)
     pr = x.copy()
     for j in range(1, 8):
         pr = pr * (x + dt(j))
-    corr = np.where(small, _ln(np.where(small, pr, dt(1)), dt), dt(0))
+    corr = np.where(small, np.log(np.where(small, pr, dt(1))), dt(0))
     x = np.where(small, x + dt(8), x)
     inv = dt(1) / x
     inv2 = inv * inv
-    ser = inv * (dt(1.0 / 12.0) - inv2 * (dt(1.0 / 360.0) - inv2 * dt(1.0 / 1260.0)))
-    return (((x - dt(0.5)) * _ln(x, dt) - x) + dt(0.91893853320467274)) + (ser - corr)
+    ser = inv * (dt(0.083333333333333333) - inv2 * (dt(0.0027777777777777778) - inv2 * dt(0.00079365079365079365)))
+    return (((x - dt(0.5)) * np.log(x) - x) + dt(0.91893853320467274)) + (ser - corr)
 
 
 def gamma(seed, idx, draw, mat, r, dt):
@@ -141,7 +148,7 @@ def poisson(seed, idx, draw, mat, lam, dt):
             if act.size == 0:
                 break
             la = la_all[act]
-            slam, loglam = np.sqrt(la), _ln(la, dt)
+            slam = np.sqrt(la)
             b = dt(0.931) + dt(2.53) * slam
             al = dt(-0.059) + dt(0.02483) * b
             invalpha = dt(1.1239) + dt(1.1328) / (b - dt(3.4))
@@ -154,9 +161,11 @@ def poisson(seed, idx, draw, mat, lam, dt):
             acc = (us >= dt(0.07)) & (V <= vr)
             rej = ~acc & ((kf < dt(0)) | ((us < dt(0.013)) & (V > us)))
             test = ~acc & ~rej
-            kt = np.where(test, kf, dt(0))
-            lhs = _ln((V * invalpha) / (al / (us * us) + b), dt)
-            rhs = (kt * loglam - la) - lfact(kt, dt)
+            # the full test in float64 from the dt-rounded V, us, kf, lam and constants (vc_cs_poisson does the same)
+            f8 = np.float64
+            kt, la8, us8 = np.where(test, kf, dt(0)).astype(f8), la.astype(f8), us.astype(f8)
+            lhs = np.log((V.astype(f8) * invalpha.astype(f8)) / (al.astype(f8) / (us8 * us8) + b.astype(f8)))
+            rhs = (kt * np.log(la8) - la8) - lfact(kt)
             acc |= test & (lhs <= rhs)
             out[act[acc]] = kf[acc].astype(np.int64)
             act = act[~acc]
@@ -186,9 +195,10 @@ def sample_counts(eta, r, seed, draw, mat, idx, dtype=np.float64):
 # ----------------------------------------------------------------------------------------------------------------------------------
 # exact moments (share nothing with the sampler) and the 6-standard-error test
 # ----------------------------------------------------------------------------------------------------------------------------------
-def exact_moments(mu, r):
-    """mean, variance, fourth central moment and P(k = 0) of Poisson(mu) (r None) or NegativeBinomial(mean mu, shape r), from the pmf
-    of torch.distributions summed in float64."""
+@lru_cache(maxsize=2)
+def exact_pmf(mu, r):
+    """(p, sd): the pmf of Poisson(mu) (r None) or NegativeBinomial(mean mu, shape r) on k = 0 .. far past its mass, from the
+    log-pmf of torch.distributions in float64 (a torch tensor), and the distribution's standard deviation."""
     mu = float(mu)
     if r is None:
         sd = math.sqrt(mu)
@@ -201,13 +211,58 @@ def exact_moments(mu, r):
     hi = int(mu + 60.0 * sd + 200)
     if r is not None and r < 1:
         hi = max(hi, int(mu / r * 400) + 1000)
-    k = torch.arange(0, hi + 1, dtype=torch.float64)
-    p = torch.exp(dist.log_prob(k))
-    assert abs(float(p.sum()) - 1.0) < 1e-9, (mu, r, float(p.sum()))
+    p = torch.exp(dist.log_prob(torch.arange(0, hi + 1, dtype=torch.float64)))
+    # 1e-8: at r = 1e6 the log-pmf's lgamma(k + r) is ~1.3e7 and its float64 rounding 2e-9 of a probability (1e-12 on GRID)
+    assert abs(float(p.sum()) - 1.0) < 1e-8, (mu, r, float(p.sum()))
+    return p, sd
+
+
+def exact_moments(mu, r):
+    """mean, variance, fourth central moment and P(k = 0) of Poisson(mu) (r None) or NegativeBinomial(mean mu, shape r), from the pmf
+    of torch.distributions summed in float64."""
+    p, _ = exact_pmf(float(mu), None if r is None else float(r))
+    k = torch.arange(0, p.shape[0], dtype=torch.float64)
     m = float((p * k).sum())
     var = float((p * (k - m) ** 2).sum())
     m4 = float((p * (k - m) ** 4).sum())
     return {"mean": m, "var": var, "m4": m4, "p0": float(p[0])}
+
+
+MIN_EXPECTED = 50.0               # gof_z merges bins until each expects this many samples
+
+
+def gof_z(k, mu, r, bins=40):
+    """Chi-square statistic of the counts `k` against the exact pmf of Poisson(mu) / NegativeBinomial(mu, r), standardised as
+    (chi2 - dof) / sqrt(2 dof).  The bins are cut at the exact cdf's j / bins quantiles (bin j = {k : e_(j-1) < k <= e_j}, near-
+    equiprobable, both end bins open); cuts that coincide (fewer support points of weight than bins) are dropped and neighbours are
+    merged until every bin expects >= MIN_EXPECTED of the len(k) samples; dof = bins left - 1."""
+    k = np.asarray(k, dtype=np.int64).reshape(-1)
+    n = k.size
+    p, _ = exact_pmf(float(mu), None if r is None else float(r))
+    cdf = torch.cumsum(p, 0).numpy()
+    edges = np.unique(np.searchsorted(cdf, np.arange(1, bins) / bins, side="left"))
+    edges = edges[edges < cdf.size - 1]
+    upper = np.concatenate([cdf[edges], [1.0]])
+    expected = n * np.diff(np.concatenate([[0.0], upper]))
+    observed = np.bincount(np.searchsorted(edges, k, side="left"), minlength=edges.size + 1).astype(np.float64)
+    # merge left to right until each bin expects enough; a short remainder joins the bin before it
+    e_m, o_m, ea, oa = [], [], 0.0, 0.0
+    for e, o in zip(expected, observed):
+        ea, oa = ea + e, oa + o
+        if ea >= MIN_EXPECTED:
+            e_m.append(ea), o_m.append(oa)
+            ea, oa = 0.0, 0.0
+    if ea > 0.0 or oa > 0.0:
+        if e_m:
+            e_m[-1], o_m[-1] = e_m[-1] + ea, o_m[-1] + oa
+        else:
+            e_m.append(ea), o_m.append(oa)
+    e_m, o_m = np.array(e_m), np.array(o_m)
+    dof = e_m.size - 1
+    assert dof >= 1, (mu, r, n, "the pmf leaves one bin: nothing to test")
+    assert o_m.sum() == n and abs(e_m.sum() - n) < 1e-6 * n
+    chi2 = float(((o_m - e_m) ** 2 / e_m).sum())
+    return (chi2 - dof) / math.sqrt(2.0 * dof)
 
 
 def moment_z(k, ex):
@@ -228,22 +283,49 @@ GRID = [(0.02, None), (3.0, None), (9.5, None), (10.5, None), (40.0, None), (300
         (0.05, 0.3), (2.0, 0.5), (12.0, 0.7), (8.0, 1.0), (11.0, 4.0), (60.0, 2.5), (150.0, 0.8), (400.0, 10.0), (9.9, 50.0), (25.0, 200.0)]
 
 
-def grid_inputs(n_per_cell):
-    """eta (float32), r (float32 or nan for Poisson), element index of the grid laid out cell after cell."""
-    eta = np.concatenate([np.full(n_per_cell, np.float32(math.log(mu)), dtype=np.float32) for mu, _ in GRID])
-    r = np.concatenate([np.full(n_per_cell, np.nan if rr is None else rr, dtype=np.float32) for _, rr in GRID])
+# rates up to the documented VC_CS_MU_MAX = 2^20.  The Poisson cells are the sensitive probe of PTRS's full test (both sides of 2^16,
+# the last just under 2^20); in the NB cells the gamma's own spread hides most of what PTRS does wrong, they hold the mixing to the
+# pmf at large rates (tests/test_ppc_cpu.py checks that the mixed rates stay inside the range)
+LARGE_GRID = [(1.0e3, None), (1.0e4, None), (6.5e4, None), (1.0e5, None), (5.0e5, None), (1.0e6, None),
+              (1.0e4, 2.0), (3.0e4, 50.0), (2.0e5, 20.0), (2.0e5, 2000.0)]
+
+
+def handed_rate(mu):
+    """exp(float64(float32(log mu))): the rate a sampler handed eta = float32(log mu) is asked for."""
+    return math.exp(float(np.float32(math.log(mu))))
+
+
+def device_r(r):
+    """The float32 r = 1 / shape_inv the device forms when it is handed shape_inv = float32(1 / r)."""
+    return np.float32(1.0) / (np.float32(1.0) / np.float32(r))
+
+
+def grid_inputs(n_per_cell, grid=None, as_device=False):
+    """eta (float32), r (float32 or nan for Poisson; device_r of the grid's r if as_device) of the grid laid out cell after cell."""
+    grid = GRID if grid is None else grid
+    eta = np.concatenate([np.full(n_per_cell, np.float32(math.log(mu)), dtype=np.float32) for mu, _ in grid])
+    r = np.concatenate([np.full(n_per_cell, np.nan if rr is None else (device_r(rr) if as_device else rr), dtype=np.float32) for _, rr in grid])
     return eta, r
 
 
-def sample_grid(n_per_cell, seed, draw, dtype):
-    """The restated sampler over GRID: Poisson cells as matrix 0, NB cells as matrix 1, element index = position in the layout."""
-    eta, r = grid_inputs(n_per_cell)
+def sample_grid(n_per_cell, seed, draw, dtype, grid=None, as_device=False):
+    """The restated sampler over a grid (GRID unless given): Poisson cells as matrix 0, NB cells as matrix 1, element index =
+    position in the layout."""
+    eta, r = grid_inputs(n_per_cell, grid, as_device)
     idx = np.arange(eta.size, dtype=np.uint64)
     out = np.empty(eta.size, dtype=np.int64)
     pois = np.isnan(r)
     out[pois] = sample_counts(eta[pois], None, seed, draw, 0, idx[pois], dtype)
     out[~pois] = sample_counts(eta[~pois], r[~pois], seed, draw, 1, idx[~pois], dtype)
     return out
+
+
+def cell_z(k, mu, r):
+    """moment_z and gof_z of one cell's counts against the exact distribution at (mu, r): {"mean", "var", "zero", "gof"}."""
+    r = None if r is None else float(r)
+    z = moment_z(k, exact_moments(mu, r))
+    z["gof"] = gof_z(k, mu, r)
+    return z
 
 
 def cap(n_diff32, n):
@@ -294,6 +376,22 @@ def replicates(z, seed, dtype=np.float64, cell_offset=0, draw0=0):
             rr = None if r is None else np.broadcast_to(r[d].numpy(), (Ng, Nc)).reshape(-1)
             rep[d] = sample_counts(e[d].reshape(-1), rr, seed, draw0 + d, mi, idx, dtype).reshape(Ng, Nc)
         out[m] = rep
+    return out
+
+
+def mixed_rates(z, seed, cell_offset=0, draw0=0):
+    """{matrix: (D, Ng, Nc) float64} the Poisson rate of every element of a fixture's draws: exp(eta), for the negative binomial
+    times gamma / r with the float64 restatement's gamma variate of that element (which does not depend on eta)."""
+    eta, r = dense_eta(z, torch.float64)
+    out = {}
+    for mi, m in enumerate(eta):
+        lam = np.exp(eta[m].numpy())
+        D, Ng, Nc = lam.shape
+        idx = element_index(Ng, Nc, cell_offset).reshape(-1)
+        for d in range(D if r is not None else 0):
+            rr = np.broadcast_to(r[d].numpy(), (Ng, Nc)).reshape(-1).copy()
+            lam[d] *= (gamma(seed, idx, draw0 + d, mi, rr, np.float64) / rr).reshape(Ng, Nc)
+        out[m] = lam
     return out
 
 

@@ -15,12 +15,16 @@
 //   lambda < 10  inversion by sequential search from k = 0 (p_0 = e^-lambda, p_k = p_(k-1) lambda / k), at most 96 terms; a uniform
 //                above the float32 sum of those terms (a rounding event of probability ~1e-7) is redrawn from the next block.
 //   lambda >= 10 Hoermann's PTRS (1993), transformed rejection with squeeze; words 0, 1 of the attempt's block.  log k! by the
-//                Stirling series to 1 / (1260 x^5) on x >= 8 (smaller arguments shifted up by the recurrence).
+//                Stirling series to 1 / (1260 x^5) on x >= 8 (smaller arguments shifted up by the recurrence).  The full acceptance
+//                test (only the attempts that pass neither the squeeze nor the quick reject reach it) is evaluated in float64.
 // Every loop is bounded by VC_CS_ATTEMPTS; running out of attempts, a lambda that is not finite or lies above VC_CS_MU_MAX returns
 // VC_CS_FAIL (-1) and the caller latches a status: a made-up value is never returned.
 //
 // The arithmetic is float32 with one rounding per written operation (no contraction), IEEE division and square root; the only
-// hardware approximations are v_exp_f32 and v_log_f32.  tests/ppc_checker.py restates the same operations in numpy.
+// hardware approximations are v_exp_f32 and v_log_f32.  The exception is PTRS's full test ln(V invalpha / (al / us^2 + b)) <=
+// k ln lam - lam - ln k!: float64 (the library's log) from the float32 V, us, k, lam and constants, because its right-hand side is
+// the difference of two terms of ~1.4e7 at lam = 1e6 where a float32 ulp is 1.  tests/ppc_checker.py restates the same operations
+// in numpy.
 #pragma once
 #include "vc_common.h"
 
@@ -40,19 +44,19 @@ __device__ __forceinline__ void vc_cs_block(uint64_t seed, uint64_t idx, uint32_
   vc_philox((uint32_t)idx, (uint32_t)(idx >> 32), draw, (mat << 16) | (stage << 8) | attempt, (uint32_t)seed, (uint32_t)(seed >> 32), w);
 }
 
-// log(k!) = lgamma(k + 1), k >= 0 an integer held in a float
-__device__ __forceinline__ float vc_cs_lfact(float k) {
-  float x = k + 1.f, corr = 0.f;
-  if (x < 8.f) {
-    float pr = x;
+// log(k!) = lgamma(k + 1), k >= 0 an integer, in float64 (PTRS's full test: see vc_cs_poisson)
+__device__ __forceinline__ double vc_cs_lfact(double k) {
+  double x = k + 1.0, corr = 0.0;
+  if (x < 8.0) {
+    double pr = x;
 #pragma unroll
-    for (int j = 1; j < 8; ++j) pr = pr * (x + (float)j);
-    corr = vc_cs_ln(pr);
-    x = x + 8.f;
+    for (int j = 1; j < 8; ++j) pr = pr * (x + (double)j);
+    corr = log(pr);
+    x = x + 8.0;
   }
-  const float inv = 1.f / x, inv2 = inv * inv;
-  const float ser = inv * (0.083333333333333333f - inv2 * (0.0027777777777777778f - inv2 * 0.00079365079365079365f));
-  return (((x - 0.5f) * vc_cs_ln(x) - x) + 0.91893853320467274f) + (ser - corr);
+  const double inv = 1.0 / x, inv2 = inv * inv;
+  const double ser = inv * (0.083333333333333333 - inv2 * (0.0027777777777777778 - inv2 * 0.00079365079365079365));
+  return (((x - 0.5) * log(x) - x) + 0.91893853320467274) + (ser - corr);
 }
 
 // gamma(r, 1) variate, r > 0; < 0: out of attempts
@@ -105,7 +109,8 @@ __device__ __forceinline__ int vc_cs_poisson(uint64_t seed, uint64_t idx, uint32
     }
     return VC_CS_FAIL;
   }
-  const float slam = __builtin_sqrtf(lam), loglam = vc_cs_ln(lam);
+  const float slam = __builtin_sqrtf(lam);
+  const double loglam = log((double)lam);
   const float b = 0.931f + 2.53f * slam;
   const float al = -0.059f + 0.02483f * b;
   const float invalpha = 1.1239f + 1.1328f / (b - 3.4f);
@@ -119,8 +124,11 @@ __device__ __forceinline__ int vc_cs_poisson(uint64_t seed, uint64_t idx, uint32
     const float kf = __builtin_floorf((((2.f * al) / us + b) * U + lam) + 0.43f);
     if (us >= 0.07f && V <= vr) return (int)kf;
     if (kf < 0.f || (us < 0.013f && V > us)) continue;
-    const float lhs = vc_cs_ln((V * invalpha) / (al / (us * us) + b));
-    const float rhs = (kf * loglam - lam) - vc_cs_lfact(kf);
+    // the full test, in float64 from the float32 V, us, kf, lam and constants: k ln lam - lam and ln k! are ~1.4e7 at lam = 1e6 and
+    // their difference is a log-probability of order -1 .. -10, lost entirely to float32's ulp of 1 there
+    const double usd = (double)us;
+    const double lhs = log(((double)V * (double)invalpha) / ((double)al / (usd * usd) + (double)b));
+    const double rhs = ((double)kf * loglam - (double)lam) - vc_cs_lfact((double)kf);
     if (lhs <= rhs) return (int)kf;
   }
   return VC_CS_FAIL;
