@@ -166,18 +166,36 @@ def assert_trajectory_within_float32_spread(spec, opt, n, seed, losses, named_pa
         assert err <= max(1e-3 * scale, 4 * spread), (k, err, spread, scale)
 
 
+# philox_eps_list pins every step's draws while n * eps_total is at most this (a numpy Philox over that many indices: well under a
+# second); past it (a slice of the 50 000-cell workload) the first and the last step, and it prints which steps it left unpinned
+ANCHOR_ALL_STEPS_UP_TO = 1 << 19
+
+
 def philox_eps_list(spec, params_flat, seed, n):
     """The standard-normal draws the performance path uses at steps 0..n-1 (Philox4x32-10 keyed by (seed, step, index)),
-    rebuilt INDEPENDENTLY of the run under test: a second engine's sampling kernel at (seed, t), read back through
-    vc_read_site(eps).  Returned as the oracle's per-site eps dicts (float64, CPU)."""
+    rebuilt by the DEVICE -- a second engine's sampling kernel at (seed, t), read back through vc_read_site(eps) -- and PINNED by
+    the float64 restatement of the stream that shares no code with it (tests/noise_checker.py): every flat vector read back must
+    equal noise_checker.normals(seed, t, global index) within noise_checker.TOL, apart from the alignment slot no site owns.
+    Returned as the oracle's per-site eps dicts (float64, CPU): the device's own float32 draws, so that the oracle replays exactly
+    what the run under test drew."""
+    from tests import noise_checker as NC
     from velocycle_amd.engine import HipEngine
     eng = HipEngine(spec)
     eng.params.copy_(params_flat.to(eng.device))
     shapes = {"ν": (spec.Ng, spec.Nh), "νω": (spec.Nx, spec.Nhw), "ϕxy": (spec.Nc, 2)}
+    owned = NC.slot_names(eng) != "align"
+    gidx = NC.global_index(eng)[owned]
+    pinned = set(range(n)) if n * eng.eps_total <= ANCHOR_ALL_STEPS_UP_TO else {0, n - 1}
+    if len(pinned) < n:
+        print(f"\n[philox_eps_list] {n} steps x {eng.eps_total} draws > {ANCHOR_ALL_STEPS_UP_TO}: steps 0 and {n - 1} are pinned to "
+              f"tests/noise_checker.py, steps 1..{n - 2} are NOT")
     out = []
     for t in range(n):
         eng.sample_guide(eps=None, seed=seed, step=t)
         flat = eng.read_site("eps")
+        if t in pinned:
+            err = np.abs(flat.double().numpy()[owned] - NC.normals(seed, t, gidx))
+            assert err.max() <= NC.TOL, (seed, t, int(err.argmax()), float(err.max()))
         out.append({k: flat[o:o + s].double().reshape(shapes.get(k, (s,))) for k, (o, s) in eng.eps_slices.items()})
     eng.close()
     return out
