@@ -35,6 +35,9 @@
  *   vc_phase_mle                Phases.from_cycle_mle (phases.py:471-509): the log-likelihood of every cell's spliced counts
  *                               on a grid of phases (ElogS / exp / Poisson | GammaPoisson log_prob / sum over genes, :499-507)
  *                               and its arg-max per cell (:508); stand-alone, no engine
+ *   vc_pca_stage, vc_pca_apply  Phases.from_pca_heuristic (phases.py:307-382): np.log(layer + small_count) and the one large
+ *                               operation of a block power iteration that replaces sklearn's PCA(n_components).fit_transform
+ *                               (:343-349); stand-alone, no engine
  *   vc_pointwise_density        no counterpart (Predictive + a traced model run per draw would be it): lppd / WAIC of every
  *                               observed count over posterior draws, summed per gene and per cell
  *   vc_sample_counts            the samplers behind pyro.sample("S" | "U", Poisson(mu) | GammaPoisson(1 / si, 1 / (si mu)))
@@ -484,6 +487,33 @@ int vc_expected_logs(vc_engine* e, const float* nu, const float* dnu, const floa
 int vc_phase_mle(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* T_dev,
                  const float* expT_dev, int bins, const float* m_dev, int noise, const float* r_dev, int32_t* best_bin_dev,
                  float* logp_rel_dev, void* hip_stream);
+
+/* --- PCA phase prior (Phases.from_pca_heuristic, phases.py:307-382): staging and the power iteration's pass ------------------
+ * Stand-alone (no engine); the iteration itself (QR, Rayleigh-Ritz on 8 x 8 matrices, float64) is the caller's:
+ * velocycle_amd/phase_prior.py.  Both calls only enqueue on hip_stream.  Errors: vc_last_error(NULL).
+ *
+ * vc_pca_stage: for cells [0, n_cells) of a dense block, X[c][g] = float32(log(raw[c][g] + small_count)) (a logarithm correct to
+ * 1 ulp), and colsum[g] += sum_c X[c][g] in float64: one partial per (64-cell tile, gene) summed in cell order, then added to
+ * colsum_dev in tile order -- a matrix staged in several calls cut at multiples of 64 cells gives the bits of one call.
+ *   raw_dev      float[n_cells][raw_stride] (raw_stride >= Ng);  X_dev: float[n_cells][x_stride] (x_stride >= Ng), the caller
+ *                passes the address of the block's first row inside the whole staged matrix
+ *   colsum_dev   double[Ng], zeroed by the caller before the first block;  partial_dev: double[ceil(n_cells / 64)][Ng] scratch
+ *   flag_dev     int32, zeroed by the caller: set to 1 (never cleared) when a staged value is not finite (v + small_count <= 0,
+ *                or v not finite)
+ * vc_pca_apply: Y = (X - mu) Q, float[Nc][8], and Z = (X - mu)^T Y, double[Ng][8], with X read from memory once.
+ *   mu_dev       float[Ng];  Q_dev: float[Ng][8], 16-byte aligned
+ *   ws_dev       float[ws_floats] scratch, 16-byte aligned, ws_floats >= vc_pca_apply_workspace(Nc, Ng, max_workgroups)
+ *                (= workgroups x Ng x 8)
+ *   max_workgroups  bound of the persistent workgroups, each of which walks ceil(tiles / workgroups) consecutive 64-cell tiles;
+ *                0 (or anything outside 1..512): 512.  It sets the size of the workspace and the order of Z's sums
+ * Sums: float32 fma chains per lane (Y: Ng / 64 terms, then a fixed tree over the 64 lanes; Z: the cells of one workgroup, at
+ * least 64), the workgroups' rows added in workgroup order in float64.  No atomics: bit-identical on repetition.  Any Nc >= 1,
+ * Ng >= 1, x_stride >= Ng. */
+int vc_pca_stage(const float* raw_dev, int64_t n_cells, int64_t Ng, int64_t raw_stride, float small_count, float* X_dev,
+                 int64_t x_stride, double* colsum_dev, double* partial_dev, int32_t* flag_dev, void* hip_stream);
+int64_t vc_pca_apply_workspace(int64_t Nc, int64_t Ng, int max_workgroups);
+int vc_pca_apply(const float* X_dev, int64_t Nc, int64_t Ng, int64_t x_stride, const float* mu_dev, const float* Q_dev,
+                 float* Y_dev, double* Z_dev, float* ws_dev, int64_t ws_floats, int max_workgroups, void* hip_stream);
 
 /* --- pointwise predictive density over posterior draws (lppd, WAIC) -------------------------------------------------------
  * The reference has no function for it (on its stack: Predictive + one traced model run per draw and a [D][Ng][Nc] tensor of

@@ -62,6 +62,8 @@ class AnnDataLite:
             self.obs.index.get_indexer(list(rows)) if _is_names(rows) else np.asarray(rows)
         cidx = np.arange(self.n_vars)[cols] if isinstance(cols, slice) else \
             self.var.index.get_indexer(list(cols)) if _is_names(cols) else np.asarray(cols)
+        # boolean masks, as anndata takes them (Phases.from_pca_heuristic selects genes_to_use with one)
+        ridx, cidx = (np.flatnonzero(i) if np.asarray(i).dtype == bool else i for i in (ridx, cidx))
         if (np.asarray(cidx) < 0).any() or (np.asarray(ridx) < 0).any():
             raise KeyError("unknown gene / cell name")
         out = AnnDataLite.__new__(AnnDataLite)

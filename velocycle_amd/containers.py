@@ -224,19 +224,34 @@ class Phases:
 
     @classmethod
     def from_pca_heuristic(cls, anndata_object, genes_to_use=None, concentration=1.0, layer="S_sz", small_count=1.0e-1,
-                           normalize_pcs=True, zero_at_min_density=False, random_state=0, plot=False, n_components=2):
+                           normalize_pcs=True, zero_at_min_density=False, random_state=0, plot=False, n_components=2, *,
+                           device=None, tol=1e-6, max_iter=200, chunk_cells=None):
         """Phase prior from the angle in the plane of the first two principal components of the log counts
-        (reference phases.py:307-382; the step right before phase inference in the tutorials)."""
-        from sklearn.decomposition import PCA
+        (reference phases.py:307-382; the step right before phase inference in the tutorials).
+        Keyword-only: with `device` ("cuda", "cuda:N"; "cpu" runs the same loop on torch) the logarithm and the components are
+        computed on the device by `velocycle_amd.phase_prior.pca_scores` (a block power iteration to `tol`, at most `max_iter`
+        passes, the layer staged in chunks of `chunk_cells` cells; `random_state` seeds its start block); `.pca` is then that
+        function's record and not an sklearn object.  With device=None: the host path, sklearn's PCA."""
         if layer not in anndata_object.layers:
             raise ValueError(f"{layer=} is not a valid entry anndata.obs")
         sub = anndata_object if genes_to_use is None else \
             anndata_object[:, [g in genes_to_use for g in anndata_object.var.index]]
         mat = sub.layers[layer]
-        mat = mat.toarray() if hasattr(mat, "toarray") else np.asarray(mat)
-        X = np.log(mat + small_count)                                   # cells x genes
-        pca = PCA(n_components, random_state=random_state)
-        pcs = pca.fit_transform(X)
+        if device is not None:
+            if plot:
+                raise ValueError("plot=True is not available with device=...: plot from the returned .pcs")
+            if n_components < 2:
+                raise ValueError("the phase is an angle in the plane of two components: n_components must be >= 2")
+            from .phase_prior import pca_scores
+            pca = pca_scores(mat, small_count, n_components, device=device, random_state=random_state, tol=tol, max_iter=max_iter,
+                             chunk_cells=chunk_cells)
+            pcs = pca.pcs.cpu().numpy()
+        else:
+            from sklearn.decomposition import PCA
+            mat = mat.toarray() if hasattr(mat, "toarray") else np.asarray(mat)
+            X = np.log(mat + small_count)                                   # cells x genes
+            pca = PCA(n_components, random_state=random_state)
+            pcs = pca.fit_transform(X)
         if normalize_pcs:
             lo, hi, med = np.percentile(pcs, [0.5, 99.5, 50], 0)
             pcs = (pcs - med) / (hi - lo)
