@@ -159,8 +159,8 @@ def test_entry_point_validates_without_a_device():
     lib = _lib.load()
     one = C.c_void_p(64)                    # never dereferenced: every call below is refused before anything is launched
 
-    def call(e, n_draws=4, gene=one, cell=one):
-        return lib.vc_pointwise_density(e, n_draws, one, 0, one, 0, None, one, None, 0, None, 0, None, 0, 0, 8, gene, cell, None, None)
+    def call(e, n_draws=4, gene=one, cell=one, phixy=one):
+        return lib.vc_pointwise_density(e, n_draws, phixy, 0, one, 0, None, one, None, 0, None, 0, None, 0, 0, 8, gene, cell, None, None)
     assert call(None) == _lib.VC_ERR_ARG and b"null engine" in lib.vc_last_error(None)
     cfg = _lib.vc_config(abi_version=_lib.VC_ABI_VERSION, model=0, guide=0, noise=0, with_delta_nu=0, n_harmonics=1, n_harmonics_w=0,
                          Nb=1, Nx=0, lrmn_rank=5, rank=0, world_size=1, Ng=5, Nc_local=8, Nc_global=8, cell_offset=0, gamma_alpha=1.0,
@@ -173,6 +173,11 @@ def test_entry_point_validates_without_a_device():
         assert call(h, gene=None) == _lib.VC_ERR_ARG and b"null gene_out_dev" in lib.vc_last_error(h)
         assert call(h, cell=None) == _lib.VC_ERR_ARG
         assert call(h) == _lib.VC_ERR_STATE and b"before vc_finalize" in lib.vc_last_error(h)
+        # a call that one of the refusals shared with vc_predictive_check would stop too (null phixy) still meets the entry point's
+        # own refusals first, in their order
+        assert call(h, n_draws=1, phixy=None) == _lib.VC_ERR_ARG and b"n_draws must be >= 2" in lib.vc_last_error(h)
+        assert call(h, gene=None, phixy=None) == _lib.VC_ERR_ARG and b"null gene_out_dev" in lib.vc_last_error(h)
+        assert call(h, phixy=None) == _lib.VC_ERR_STATE and b"before vc_finalize" in lib.vc_last_error(h)
     finally:
         lib.vc_destroy(h)
 

@@ -265,8 +265,8 @@ def test_entry_points_validate_without_a_device():
     assert lib.vc_sample_counts(one, 1, 1, None, 1, -1, 0, 0, 1, one, None) == _lib.VC_ERR_ARG and b"draw" in lib.vc_last_error(None)
     assert lib.vc_sample_counts(one, 1, 1, None, 1, 0, 1 << 16, 0, 1, one, None) == _lib.VC_ERR_ARG
 
-    def call(e, n_draws=4, gene=one, cell=one, d0=0, nd=4):
-        return lib.vc_predictive_check(e, n_draws, one, 0, one, 0, None, one, None, 0, None, 0, None, 0, 7, 0, 8, d0, nd, gene, cell, None, None,
+    def call(e, n_draws=4, gene=one, cell=one, d0=0, nd=4, phixy=one):
+        return lib.vc_predictive_check(e, n_draws, phixy, 0, one, 0, None, one, None, 0, None, 0, None, 0, 7, 0, 8, d0, nd, gene, cell, None, None,
                                        None, 0, None)
     assert call(None) == _lib.VC_ERR_ARG and b"null engine" in lib.vc_last_error(None)
     cfg = _lib.vc_config(abi_version=_lib.VC_ABI_VERSION, model=0, guide=0, noise=0, with_delta_nu=0, n_harmonics=1, n_harmonics_w=0,
@@ -279,6 +279,11 @@ def test_entry_points_validate_without_a_device():
         assert call(h, gene=None) == _lib.VC_ERR_ARG and b"null gene_rep_dev" in lib.vc_last_error(h)
         assert call(h, cell=None) == _lib.VC_ERR_ARG
         assert call(h) == _lib.VC_ERR_STATE and b"before vc_finalize" in lib.vc_last_error(h)
+        # a call that one of the refusals shared with vc_pointwise_density would stop too (null phixy) still meets the entry point's
+        # own refusals first, in their order
+        assert call(h, n_draws=0, phixy=None) == _lib.VC_ERR_ARG and b"n_draws must be >= 1" in lib.vc_last_error(h)
+        assert call(h, gene=None, phixy=None) == _lib.VC_ERR_ARG and b"null gene_rep_dev" in lib.vc_last_error(h)
+        assert call(h, phixy=None) == _lib.VC_ERR_STATE and b"before vc_finalize" in lib.vc_last_error(h)
     finally:
         lib.vc_destroy(h)
 

@@ -1021,18 +1021,22 @@ void vc_launch_scatter_csr(const long long* indptr, const int* indices, const fl
 void vc_launch_expected_logs(const VcDims& d, const VcBufs& b, const float* nu, const float* dnu, const float* phi,
                              const float* omega, const float* logbeta, const float* gamma, float cf_avg, float* out_S,
                              float* out_S2, float* out_U, float* out_U2, hipStream_t st);
-// pointwise predictive density over posterior draws (vc_pointwise.hip): what one launch reads and writes
-struct VcPwArgs {
+// what every launch that evaluates the model under posterior draws reads (vc_draw_model.h): the engine's counts and cell data, the draws
+struct VcDrawArgs {
   const void *S, *U;                  // blocked counts as vc_finalize left them (c16: uint16, else float32)
   const float *cf, *Dm, *Dbm;         // (Nc), (Nx, Nc), (Nb, Nc) in the caller's cell order
   const int* cell_pos;                // position of cell c in the blocked counts, or nullptr: the identity
+  const float *phixy, *nu, *dnu, *shape_inv, *loggamma, *logbeta, *nuomega;      // the draws of every site (dnu, shape_inv: one value)
+  long long phixy_ds, nu_ds, lg_ds, lb_ds, nw_ds;                                // their draw strides in floats (0: the same in every draw)
+  int Ng, Nc, gbw, Nb, Nx, Hw, c16;
+  int c_begin, c_end;                 // cells [c_begin, c_end) of the launch
+};
+// pointwise predictive density over posterior draws (vc_pointwise.hip): what one launch reads and writes
+struct VcPwArgs : VcDrawArgs {        // c_begin: a multiple of 64; workgroup w: cells c_begin + 64 w ...
   const int* h_ptr;                   // histogram CSR [2 Ng + 1]
   const float* h_val;                 // its count values, ascending within a gene
   const double* h_lgc;                // per entry: lgamma(r + k) - lgamma(r) - lgamma(k + 1) (Poisson: -lgamma(k + 1))
-  const float *phixy, *nu, *dnu, *shape_inv, *loggamma, *logbeta, *nuomega;      // the draws of every site (dnu, shape_inv: one value)
-  long long phixy_ds, nu_ds, lg_ds, lb_ds, nw_ds;                                // their draw strides in floats (0: the same in every draw)
-  int n_draws, Ng, Nc, gbw, Nb, Nx, Hw, c16;
-  int c_begin, c_end;                 // cells [c_begin, c_end) of this launch, c_begin a multiple of 64; workgroup w: cells c_begin + 64 w ...
+  int n_draws;
   double* ws;                         // [workgroups][3 nmat][Ng] per-gene partial rows of the launch
   double* cell_out;                   // [3 nmat][Nc]
   float* dense;                       // [nmat][Ng][Nc] lppd per element, or nullptr
@@ -1042,17 +1046,10 @@ struct VcPwArgs {
 int vc_launch_pointwise(const VcPwArgs& a, int H, int kind, int noise, int n_super, double* gene_out, hipStream_t st);
 void vc_launch_pw_const(int n_entries, int Ng, int nmat, const int* h_ptr, const float* h_val, const float* shape_inv, int noise,
                         double* out, hipStream_t st);
-// posterior predictive check (vc_ppc.hip): what one call's launches read and write
-struct VcPpcArgs {
-  const void *S, *U;                  // blocked counts as vc_finalize left them (c16: uint16, else float32): the observed statistics
-  const float *cf, *Dm, *Dbm;         // (Nc), (Nx, Nc), (Nb, Nc) in the caller's cell order
-  const int* cell_pos;                // position of cell c in the blocked counts, or nullptr: the identity
-  const float *phixy, *nu, *dnu, *shape_inv, *loggamma, *logbeta, *nuomega;      // the draws of every site (dnu, shape_inv: one value)
-  long long phixy_ds, nu_ds, lg_ds, lb_ds, nw_ds;                                // their draw strides in floats (0: the same in every draw)
+// posterior predictive check (vc_ppc.hip): what one call's launches read and write (S, U: the observed statistics)
+struct VcPpcArgs : VcDrawArgs {
   uint64_t seed;                      // Philox key
   long long cell_offset;              // global index of local cell 0 (the sampler's element index takes the GLOBAL cell)
-  int Ng, Nc, gbw, Nb, Nx, Hw, c16;
-  int c_begin, c_end;                 // cells [c_begin, c_end) of the call
   int d_begin;                        // first draw of the launch (workgroup row y: draw d_begin + y)
   int n_keep;                         // dense replicates are stored for the draws < n_keep
   unsigned long long* gene_rep;       // [D][nmat][4][Ng]  sum k, sum k^2, #{k = 0}, max k over the cells: integer atomics

@@ -1990,6 +1990,37 @@ extern "C" int vc_expected_logs(vc_engine* e, const float* nu, const float* dnu,
 // workgroups (64 cells each) per launch of vc_pointwise_density: bounds its only workspace, [PW_MAX_SUPER][3 nmat][Ng] doubles
 static const int PW_MAX_SUPER = 512;
 
+// What vc_pointwise_density and vc_predictive_check (`fn`) share once their own arguments are checked: the refusals of a model or a
+// set of draws that the draw kernels (vc_draw_model.h) do not cover, then everything of `a` but the cell range.  reads_U: the call
+// reads the engine's unspliced counts when the model has them.
+static int draw_args(vc_engine* e, const char* fn, bool reads_U, const float* phixy, int64_t phixy_stride, const float* nu, int64_t nu_stride,
+                     const float* dnu, const float* shape_inv, const float* loggamma, int64_t loggamma_stride, const float* logbeta,
+                     int64_t logbeta_stride, const float* nuomega, int64_t nuomega_stride, VcDrawArgs& a) {
+  const VcDims& d = e->d;
+  const VcBufs& b = e->b;
+  if (d.noise == VC_NOISE_LOGNORMAL)
+    return e->fail(VC_ERR_UNSUPPORTED, "%s: Lognormal noise is not supported (NegativeBinomial or Poisson)", fn);
+  if (d.generic || d.H < 1 || d.H > VC_MAXH || d.Hw > VC_MAXH)
+    return e->fail(VC_ERR_UNSUPPORTED, "%s: this engine runs the run-time-sized kernel set (H = %d, Hw = %d, Nb = %d, LRMN rank %d, "
+                   "%d angular-speed coefficients): only what the compiled fast set covers is supported", fn, d.H, d.Hw, d.Nb, d.R, d.NW);
+  const bool vel = d.model == VC_MODEL_VELOCITY, nb = d.noise == VC_NOISE_NB;
+  const int nbat = d.with_dnu ? d.Nb : 0;
+  if (!phixy || !nu) return e->fail(VC_ERR_ARG, "%s: null phixy / nu", fn);
+  if (nbat > 0 && !dnu) return e->fail(VC_ERR_ARG, "%s: the model has batch offsets, dnu is required", fn);
+  if (nb && !shape_inv) return e->fail(VC_ERR_ARG, "%s: the negative binomial needs shape_inv", fn);
+  if (vel && (!loggamma || !logbeta || !nuomega)) return e->fail(VC_ERR_ARG, "%s: null loggamma / logbeta / nuomega", fn);
+  if (vel && reads_U && !b.U) return e->fail(VC_ERR_STATE, "%s: the engine holds no unspliced counts", fn);
+  auto stride_ok = [](int64_t s, long long full) { return s == 0 || s == full; };
+  if (!stride_ok(phixy_stride, 2LL * d.Nc) || !stride_ok(nu_stride, (long long)d.Ng * d.Nh) ||
+      (vel && (!stride_ok(loggamma_stride, d.Ng) || !stride_ok(logbeta_stride, d.Ng) || !stride_ok(nuomega_stride, d.NW))))
+    return e->fail(VC_ERR_ARG, "%s: a draw stride must be 0 or the length of its site", fn);
+  a.S = b.S; a.U = b.U; a.cf = b.cf; a.Dm = b.Dm; a.Dbm = b.Dbm; a.cell_pos = b.cell_pos;
+  a.phixy = phixy; a.nu = nu; a.dnu = dnu; a.shape_inv = shape_inv; a.loggamma = loggamma; a.logbeta = logbeta; a.nuomega = nuomega;
+  a.phixy_ds = phixy_stride; a.nu_ds = nu_stride; a.lg_ds = loggamma_stride; a.lb_ds = logbeta_stride; a.nw_ds = nuomega_stride;
+  a.Ng = d.Ng; a.Nc = d.Nc; a.gbw = d.gbw; a.Nb = nbat; a.Nx = d.Nx; a.Hw = d.Hw; a.c16 = d.c16;
+  return VC_OK;
+}
+
 extern "C" int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* phixy, int64_t phixy_stride, const float* nu,
                                     int64_t nu_stride, const float* dnu, const float* shape_inv, const float* loggamma,
                                     int64_t loggamma_stride, const float* logbeta, int64_t logbeta_stride, const float* nuomega,
@@ -2003,22 +2034,10 @@ extern "C" int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* 
   if (!e->finalized) return e->fail(VC_ERR_STATE, "vc_pointwise_density before vc_finalize");
   const VcDims& d = e->d;
   const VcBufs& b = e->b;
-  if (d.noise == VC_NOISE_LOGNORMAL)
-    return e->fail(VC_ERR_UNSUPPORTED, "vc_pointwise_density: Lognormal noise is not supported (NegativeBinomial or Poisson)");
-  if (d.generic || d.H < 1 || d.H > VC_MAXH || d.Hw > VC_MAXH)
-    return e->fail(VC_ERR_UNSUPPORTED, "vc_pointwise_density: this engine runs the run-time-sized kernel set (H = %d, Hw = %d, Nb = %d, LRMN rank %d, "
-                   "%d angular-speed coefficients): only what the compiled fast set covers is supported", d.H, d.Hw, d.Nb, d.R, d.NW);
-  const bool vel = d.model == VC_MODEL_VELOCITY, nb = d.noise == VC_NOISE_NB;
-  const int nbat = d.with_dnu ? d.Nb : 0;
-  if (!phixy || !nu) return e->fail(VC_ERR_ARG, "vc_pointwise_density: null phixy / nu");
-  if (nbat > 0 && !dnu) return e->fail(VC_ERR_ARG, "vc_pointwise_density: the model has batch offsets, dnu is required");
-  if (nb && !shape_inv) return e->fail(VC_ERR_ARG, "vc_pointwise_density: the negative binomial needs shape_inv");
-  if (vel && (!loggamma || !logbeta || !nuomega)) return e->fail(VC_ERR_ARG, "vc_pointwise_density: null loggamma / logbeta / nuomega");
-  if (vel && !b.U) return e->fail(VC_ERR_STATE, "vc_pointwise_density: the engine holds no unspliced counts");
-  auto stride_ok = [](int64_t s, long long full) { return s == 0 || s == full; };
-  if (!stride_ok(phixy_stride, 2LL * d.Nc) || !stride_ok(nu_stride, (long long)d.Ng * d.Nh) ||
-      (vel && (!stride_ok(loggamma_stride, d.Ng) || !stride_ok(logbeta_stride, d.Ng) || !stride_ok(nuomega_stride, d.NW))))
-    return e->fail(VC_ERR_ARG, "vc_pointwise_density: a draw stride must be 0 or the length of its site");
+  const bool vel = d.model == VC_MODEL_VELOCITY;
+  VcPwArgs a{};
+  TRY(draw_args(e, "vc_pointwise_density", true, phixy, phixy_stride, nu, nu_stride, dnu, shape_inv, loggamma, loggamma_stride, logbeta,
+                logbeta_stride, nuomega, nuomega_stride, a));
   if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > d.Nc || (cell_begin & 63))
     return e->fail(VC_ERR_ARG, "vc_pointwise_density: cells [%lld, %lld) must lie in [0, %d) and start at a multiple of 64",
                    (long long)cell_begin, (long long)(cell_begin + cell_count), d.Nc);
@@ -2038,12 +2057,8 @@ extern "C" int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* 
     TRY(e->dalloc(&e->pw_ws, supers * NQ * (size_t)d.Ng));
   }
   vc_launch_pw_const(n_entries, d.Ng, 2, b.h_ptr, e->pw_val, shape_inv, d.noise, e->pw_lgc, st);
-  VcPwArgs a{};
-  a.S = b.S; a.U = b.U; a.cf = b.cf; a.Dm = b.Dm; a.Dbm = b.Dbm; a.cell_pos = b.cell_pos;
   a.h_ptr = b.h_ptr; a.h_val = e->pw_val; a.h_lgc = e->pw_lgc;
-  a.phixy = phixy; a.nu = nu; a.dnu = dnu; a.shape_inv = shape_inv; a.loggamma = loggamma; a.logbeta = logbeta; a.nuomega = nuomega;
-  a.phixy_ds = phixy_stride; a.nu_ds = nu_stride; a.lg_ds = loggamma_stride; a.lb_ds = logbeta_stride; a.nw_ds = nuomega_stride;
-  a.n_draws = (int)n_draws; a.Ng = d.Ng; a.Nc = d.Nc; a.gbw = d.gbw; a.Nb = nbat; a.Nx = d.Nx; a.Hw = d.Hw; a.c16 = d.c16;
+  a.n_draws = (int)n_draws;
   a.ws = e->pw_ws; a.cell_out = cell_out_dev; a.dense = dense_lppd_dev;
   // everything eta_S depends on is the same in every draw: the S matrix is evaluated once
   const int kind = !vel ? 0 : ((phixy_stride == 0 && nu_stride == 0) ? 2 : 1);
@@ -2068,6 +2083,7 @@ extern "C" int vc_predictive_check(vc_engine* e, int64_t n_draws, const float* p
                                    int64_t draw_count, int64_t* gene_rep_dev, int64_t* cell_rep_dev, double* gene_obs_dev,
                                    double* cell_obs_dev, int32_t* keep_dev, int64_t n_keep, void* hip_stream) {
   if (!e) { vc_set_global_error("vc_predictive_check: null engine"); return VC_ERR_ARG; }
+  VC_GUARD_BEGIN
   if (n_draws < 1) return e->fail(VC_ERR_ARG, "vc_predictive_check: n_draws must be >= 1");
   if (n_draws > (1 << 20)) return e->fail(VC_ERR_ARG, "vc_predictive_check: more than 2^20 draws");
   if (!gene_rep_dev || !cell_rep_dev) return e->fail(VC_ERR_ARG, "vc_predictive_check: null gene_rep_dev / cell_rep_dev");
@@ -2076,22 +2092,10 @@ extern "C" int vc_predictive_check(vc_engine* e, int64_t n_draws, const float* p
   if (!e->finalized) return e->fail(VC_ERR_STATE, "vc_predictive_check before vc_finalize");
   const VcDims& d = e->d;
   const VcBufs& b = e->b;
-  if (d.noise == VC_NOISE_LOGNORMAL)
-    return e->fail(VC_ERR_UNSUPPORTED, "vc_predictive_check: Lognormal noise is not supported (NegativeBinomial or Poisson)");
-  if (d.generic || d.H < 1 || d.H > VC_MAXH || d.Hw > VC_MAXH)
-    return e->fail(VC_ERR_UNSUPPORTED, "vc_predictive_check: this engine runs the run-time-sized kernel set (H = %d, Hw = %d, Nb = %d, LRMN rank %d, "
-                   "%d angular-speed coefficients): only what the compiled fast set covers is supported", d.H, d.Hw, d.Nb, d.R, d.NW);
   const bool vel = d.model == VC_MODEL_VELOCITY, nb = d.noise == VC_NOISE_NB;
-  const int nbat = d.with_dnu ? d.Nb : 0;
-  if (!phixy || !nu) return e->fail(VC_ERR_ARG, "vc_predictive_check: null phixy / nu");
-  if (nbat > 0 && !dnu) return e->fail(VC_ERR_ARG, "vc_predictive_check: the model has batch offsets, dnu is required");
-  if (nb && !shape_inv) return e->fail(VC_ERR_ARG, "vc_predictive_check: the negative binomial needs shape_inv");
-  if (vel && (!loggamma || !logbeta || !nuomega)) return e->fail(VC_ERR_ARG, "vc_predictive_check: null loggamma / logbeta / nuomega");
-  if (vel && gene_obs_dev && !b.U) return e->fail(VC_ERR_STATE, "vc_predictive_check: the engine holds no unspliced counts");
-  auto stride_ok = [](int64_t s, long long full) { return s == 0 || s == full; };
-  if (!stride_ok(phixy_stride, 2LL * d.Nc) || !stride_ok(nu_stride, (long long)d.Ng * d.Nh) ||
-      (vel && (!stride_ok(loggamma_stride, d.Ng) || !stride_ok(logbeta_stride, d.Ng) || !stride_ok(nuomega_stride, d.NW))))
-    return e->fail(VC_ERR_ARG, "vc_predictive_check: a draw stride must be 0 or the length of its site");
+  VcPpcArgs a{};
+  TRY(draw_args(e, "vc_predictive_check", gene_obs_dev != nullptr, phixy, phixy_stride, nu, nu_stride, dnu, shape_inv, loggamma,
+                loggamma_stride, logbeta, logbeta_stride, nuomega, nuomega_stride, a));
   if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > d.Nc)
     return e->fail(VC_ERR_ARG, "vc_predictive_check: cells [%lld, %lld) must lie in [0, %d)", (long long)cell_begin,
                    (long long)(cell_begin + cell_count), d.Nc);
@@ -2101,12 +2105,7 @@ extern "C" int vc_predictive_check(vc_engine* e, int64_t n_draws, const float* p
   if (n_keep < 0 || n_keep > n_draws || (n_keep > 0) != (keep_dev != nullptr))
     return e->fail(VC_ERR_ARG, "vc_predictive_check: n_keep must lie in [0, n_draws] and come with keep_dev");
   hipStream_t st = (hipStream_t)hip_stream;
-  VcPpcArgs a{};
-  a.S = b.S; a.U = b.U; a.cf = b.cf; a.Dm = b.Dm; a.Dbm = b.Dbm; a.cell_pos = b.cell_pos;
-  a.phixy = phixy; a.nu = nu; a.dnu = dnu; a.shape_inv = shape_inv; a.loggamma = loggamma; a.logbeta = logbeta; a.nuomega = nuomega;
-  a.phixy_ds = phixy_stride; a.nu_ds = nu_stride; a.lg_ds = loggamma_stride; a.lb_ds = logbeta_stride; a.nw_ds = nuomega_stride;
   a.seed = seed; a.cell_offset = d.cell_offset;
-  a.Ng = d.Ng; a.Nc = d.Nc; a.gbw = d.gbw; a.Nb = nbat; a.Nx = d.Nx; a.Hw = d.Hw; a.c16 = d.c16;
   a.c_begin = (int)cell_begin; a.c_end = (int)(cell_begin + cell_count); a.d_begin = (int)draw_begin; a.n_keep = (int)n_keep;
   a.gene_rep = (unsigned long long*)gene_rep_dev; a.cell_rep = (unsigned long long*)cell_rep_dev;
   a.gene_obs = gene_obs_dev; a.cell_obs = cell_obs_dev; a.keep = keep_dev;
@@ -2125,6 +2124,7 @@ extern "C" int vc_predictive_check(vc_engine* e, int64_t n_draws, const float* p
                    "shape_inv <= 0, or a rejection loop out of attempts) since the last vc_clear_status; the tables of this call are not valid",
                    bad);
   return VC_OK;
+  VC_GUARD_END(e)
 }
 
 extern "C" int vc_read_site(vc_engine* e, int site, float* host_out, int64_t n, void* hip_stream) {

@@ -24,6 +24,7 @@
 // Every product-sum below is written as the fma it is meant to be; nothing else may be contracted: a ragged tile then performs the
 // operations of a full one.
 #pragma clang fp contract(off)
+#include "vc_draw_model.h"      // eta_S / eta_U of one (draw, gene, cell) and the count access, shared with vc_ppc.hip
 
 namespace {
 
@@ -72,12 +73,6 @@ __device__ __forceinline__ double pw_const(const VcPwArgs& a, int mat, int g, fl
   return __builtin_nan("");                  // a count the histogram does not list: cannot happen on a finalized engine
 }
 
-template <bool U16>
-__device__ __forceinline__ float pw_count(const void* p, size_t i) {
-  if (U16) return (float)((const unsigned short*)p)[i];
-  return ((const float*)p)[i];
-}
-
 // KIND 0: phase model (S) | 1: velocity (S and U per draw) | 2: velocity, everything eta_S depends on is the same in every draw
 template <int H, int KIND, int NOISE, bool U16, int TC>
 __global__ __launch_bounds__(PW_NW * 64) void vc_pointwise_kernel(const VcPwArgs a) {
@@ -119,12 +114,10 @@ __global__ __launch_bounds__(PW_NW * 64) void vc_pointwise_kernel(const VcPwArgs
         const int c_raw = cs0 + t0 + t;
         const int c = c_raw < a.c_end ? c_raw : a.c_end - 1;                 // wave-uniform
         const int pos = a.cell_pos ? a.cell_pos[c] : c;
-        const size_t idx = (lay_blk * (size_t)a.Nc + (size_t)pos) * (size_t)a.gbw + lay_in;
-        kS[t] = pw_count<U16>(a.S, idx);
-        kU[t] = VEL ? pw_count<U16>(a.U, idx) : 0.f;
-        float e = a.cf[c];
-        for (int q = 0; q < a.Nb; ++q) e = __builtin_fmaf(a.Dbm[(size_t)q * a.Nc + c], a.dnu[(size_t)q * a.Ng + g], e);
-        e0[t] = e * VC_LOG2E;
+        const size_t idx = vc_dm_count_index(lay_blk, a.Nc, pos, a.gbw, lay_in);
+        kS[t] = vc_dm_count<U16>(a.S, idx);
+        kU[t] = VEL ? vc_dm_count<U16>(a.U, idx) : 0.f;
+        e0[t] = vc_dm_e0(a.cf[c], a.Dbm, a.dnu, a.Nb, a.Nc, a.Ng, c, g);
         etaS[t] = 0.f;
       }
       PwState stS[TC], stU[TC];
@@ -138,39 +131,12 @@ __global__ __launch_bounds__(PW_NW * 64) void vc_pointwise_kernel(const VcPwArgs
         const bool first = dr == 0;
         if (first || rec_var) {
           const float* xy = a.phixy + (size_t)dr * a.phixy_ds + 2 * (size_t)cm;
-          float s1, c1;
-          vc_dir_sincos(xy[0], xy[1], &s1, &c1);
-          sk[0] = s1; ck[0] = c1;
-#pragma unroll
-          for (int k = 1; k < VC_MAXH; ++k) {
-            sk[k] = sk[k - 1] * c1 + ck[k - 1] * s1;
-            ck[k] = ck[k - 1] * c1 - sk[k - 1] * s1;
-          }
+          vc_dm_basis(xy[0], xy[1], sk, ck);
         }
-        if (VEL && (first || om_var)) {
-          const float* nw = a.nuomega + (size_t)dr * a.nw_ds;
-          const int nhw = 2 * a.Hw + 1;
-          float omega = 0.f;
-          for (int xq = 0; xq < a.Nx; ++xq) {
-            float o = nw[xq * nhw];
-#pragma unroll
-            for (int k = 0; k < VC_MAXH; ++k)
-              if (k < a.Hw) o += nw[xq * nhw + 2 * k + 1] * sk[k] + nw[xq * nhw + 2 * k + 2] * ck[k];
-            omega += a.Dm[(size_t)xq * a.Nc + cm] * o;
-          }
-          oml = omega * VC_LN2;
-        }
+        if (VEL && (first || om_var)) oml = vc_dm_omega_l2(a.nuomega + (size_t)dr * a.nw_ds, a.Dm, a.Nx, a.Hw, a.Nc, cm, sk, ck);
         // this gene's latents of draw dr, in log2 units
         float an[NH], gam = 0.f, lb2 = 0.f;
-        {
-          const float* nud = a.nu + (size_t)dr * a.nu_ds + (size_t)g * NH;
-#pragma unroll
-          for (int h = 0; h < NH; ++h) an[h] = nud[h] * VC_LOG2E;
-          if (VEL) {
-            gam = __builtin_amdgcn_exp2f(a.loggamma[(size_t)dr * a.lg_ds + g] * VC_LOG2E);
-            lb2 = a.logbeta[(size_t)dr * a.lb_ds + g] * VC_LOG2E;
-          }
-        }
+        vc_dm_latents<H, VEL>(a.nu, a.nu_ds, a.loggamma, a.lg_ds, a.logbeta, a.lb_ds, dr, g, an, gam, lb2);
         const float inv_n = 1.f / (float)(dr + 1);
 #pragma unroll
         for (int t = 0; t < TC; ++t) {
@@ -178,26 +144,11 @@ __global__ __launch_bounds__(PW_NW * 64) void vc_pointwise_kernel(const VcPwArgs
 #pragma unroll
           for (int k = 0; k < H; ++k) { sc[k] = pw_rl(sk[k], t); cc[k] = pw_rl(ck[k], t); }
           if (!SINV || first) {
-            float eta = an[0] + e0[t];
-#pragma unroll
-            for (int k = 0; k < H; ++k) {
-              eta = __builtin_fmaf(an[2 * k + 1], sc[k], eta);
-              eta = __builtin_fmaf(an[2 * k + 2], cc[k], eta);
-            }
-            etaS[t] = eta;
-            pw_update(stS[t], pw_lik<NOISE>(kS[t], eta, r, rl2), first, inv_n);
+            etaS[t] = vc_dm_eta_S<H>(an, e0[t], sc, cc);
+            pw_update(stS[t], pw_lik<NOISE>(kS[t], etaS[t], r, rl2), first, inv_n);
           }
           if (VEL) {
-            const float om = pw_rl(oml, t);
-            float dd = 0.f;
-#pragma unroll
-            for (int k = 0; k < H; ++k) {
-              dd = __builtin_fmaf((float)(k + 1) * an[2 * k + 1], cc[k], dd);
-              dd = __builtin_fmaf(-(float)(k + 1) * an[2 * k + 2], sc[k], dd);
-            }
-            const float z = __builtin_fmaf(dd, om, gam);
-            const float zz = __builtin_fmaxf(z, 0.f) + 1e-5f;
-            const float etaU = (etaS[t] - lb2) + __builtin_amdgcn_logf(zz);
+            const float etaU = vc_dm_eta_U<H>(an, etaS[t], lb2, gam, pw_rl(oml, t), sc, cc);
             pw_update(stU[t], pw_lik<NOISE>(kU[t], etaU, r, rl2), first, inv_n);
           }
         }

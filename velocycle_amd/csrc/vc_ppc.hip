@@ -6,7 +6,7 @@
 // Mapping.  Grid (64-cell blocks of the call's range, draws of the call's range); a workgroup owns ONE draw and 64 consecutive cells
 // (in the caller's order), lane = cell.  A lane forms its cell's record once (sin / cos of k phi, omega, count factor); the
 // PPC_NW waves deal out the genes (gene = wave + PPC_NW i: wave-uniform, its latents arrive through scalar loads).  eta_S / eta_U are
-// the expressions of vc_pointwise.hip in the same log2 units.
+// the statements of vc_draw_model.h, the ones vc_pointwise.hip scores the observed counts with.
 //
 // Sums.  All replicate statistics are integers.  Per (gene, matrix) a wave reduces its 64 cells' k, k^2, [k = 0] and max k by
 // xor-shuffles and lane 0 adds them to the [D][nmat][4][Ng] table with 64-bit integer atomics (atomicAdd / atomicMax): exact, so
@@ -14,6 +14,7 @@
 // lane, added over the waves through the LDS in wave order and stored by the one workgroup that owns (draw, cell).  No float atomics.
 // The observed statistics come from the engine's own copy of the counts in a fixed order (vc_ppc_observed_*).
 #include "vc_count_sampler.h"
+#include "vc_draw_model.h"      // behind the sampler's `#pragma clang fp contract(off)`
 #include <mutex>
 
 void vc_set_global_error(const char* msg);      // vc_engine.hip: the message vc_last_error(NULL) returns
@@ -57,27 +58,8 @@ __global__ __launch_bounds__(PPC_NW * 64) void vc_ppc_kernel(const VcPpcArgs a) 
   float sk[VC_MAXH], ck[VC_MAXH], oml = 0.f;
   {
     const float* xy = a.phixy + (size_t)dr * a.phixy_ds + 2 * (size_t)c;
-    float s1, c1;
-    vc_dir_sincos(xy[0], xy[1], &s1, &c1);
-    sk[0] = s1; ck[0] = c1;
-#pragma unroll
-    for (int k = 1; k < VC_MAXH; ++k) {
-      sk[k] = sk[k - 1] * c1 + ck[k - 1] * s1;
-      ck[k] = ck[k - 1] * c1 - sk[k - 1] * s1;
-    }
-    if (VEL) {
-      const float* nw = a.nuomega + (size_t)dr * a.nw_ds;
-      const int nhw = 2 * a.Hw + 1;
-      float omega = 0.f;
-      for (int xq = 0; xq < a.Nx; ++xq) {
-        float o = nw[xq * nhw];
-#pragma unroll
-        for (int k = 0; k < VC_MAXH; ++k)
-          if (k < a.Hw) o += nw[xq * nhw + 2 * k + 1] * sk[k] + nw[xq * nhw + 2 * k + 2] * ck[k];
-        omega += a.Dm[(size_t)xq * a.Nc + c] * o;
-      }
-      oml = omega * VC_LN2;
-    }
+    vc_dm_basis(xy[0], xy[1], sk, ck);
+    if (VEL) oml = vc_dm_omega_l2(a.nuomega + (size_t)dr * a.nw_ds, a.Dm, a.Nx, a.Hw, a.Nc, c, sk, ck);
   }
   const float cf = a.cf[c];
   u64 lib[NM];
@@ -89,37 +71,12 @@ __global__ __launch_bounds__(PPC_NW * 64) void vc_ppc_kernel(const VcPpcArgs a) 
   for (int g = wave; g < a.Ng; g += PPC_NW) {
     float r = 0.f;
     if (NB) r = 1.f / a.shape_inv[g];
-    float e = cf;
-    for (int q = 0; q < a.Nb; ++q) e = __builtin_fmaf(a.Dbm[(size_t)q * a.Nc + c], a.dnu[(size_t)q * a.Ng + g], e);
-    const float e0 = e * VC_LOG2E;
+    const float e0 = vc_dm_e0(cf, a.Dbm, a.dnu, a.Nb, a.Nc, a.Ng, c, g);
     float an[NH], gam = 0.f, lb2 = 0.f;
-    {
-      const float* nud = a.nu + (size_t)dr * a.nu_ds + (size_t)g * NH;
-#pragma unroll
-      for (int h = 0; h < NH; ++h) an[h] = nud[h] * VC_LOG2E;
-      if (VEL) {
-        gam = __builtin_amdgcn_exp2f(a.loggamma[(size_t)dr * a.lg_ds + g] * VC_LOG2E);
-        lb2 = a.logbeta[(size_t)dr * a.lb_ds + g] * VC_LOG2E;
-      }
-    }
+    vc_dm_latents<H, VEL>(a.nu, a.nu_ds, a.loggamma, a.lg_ds, a.logbeta, a.lb_ds, dr, g, an, gam, lb2);
     float eta[NM];
-    eta[0] = an[0] + e0;
-#pragma unroll
-    for (int k = 0; k < H; ++k) {
-      eta[0] = __builtin_fmaf(an[2 * k + 1], sk[k], eta[0]);
-      eta[0] = __builtin_fmaf(an[2 * k + 2], ck[k], eta[0]);
-    }
-    if (VEL) {
-      float dd = 0.f;
-#pragma unroll
-      for (int k = 0; k < H; ++k) {
-        dd = __builtin_fmaf((float)(k + 1) * an[2 * k + 1], ck[k], dd);
-        dd = __builtin_fmaf(-(float)(k + 1) * an[2 * k + 2], sk[k], dd);
-      }
-      const float z = __builtin_fmaf(dd, oml, gam);
-      const float zz = __builtin_fmaxf(z, 0.f) + 1e-5f;
-      eta[NM - 1] = (eta[0] - lb2) + __builtin_amdgcn_logf(zz);
-    }
+    eta[0] = vc_dm_eta_S<H>(an, e0, sk, ck);
+    if (VEL) eta[NM - 1] = vc_dm_eta_U<H>(an, eta[0], lb2, gam, oml, sk, ck);
     const uint64_t idx = ((uint64_t)g << 32) | gcell;
 #pragma unroll
     for (int m = 0; m < NM; ++m) {
@@ -154,12 +111,6 @@ __global__ __launch_bounds__(PPC_NW * 64) void vc_ppc_kernel(const VcPpcArgs a) 
   }
 }
 
-template <bool U16>
-__device__ __forceinline__ double ppc_count(const void* p, size_t i) {
-  if (U16) return (double)((const unsigned short*)p)[i];
-  return (double)((const float*)p)[i];
-}
-
 // observed counts, per gene over the cells [c_begin, c_end) in the caller's order, continued from what gene_obs holds: one thread per
 // (matrix, gene), a fixed order of float64 additions
 template <bool U16>
@@ -173,7 +124,7 @@ __global__ __launch_bounds__(64) void vc_ppc_observed_gene_kernel(const VcPpcArg
   const size_t lay_blk = (size_t)(g / a.gbw), lay_in = (size_t)(g % a.gbw);
   for (int c = a.c_begin; c < a.c_end; ++c) {
     const int pos = a.cell_pos ? a.cell_pos[c] : c;
-    const double k = ppc_count<U16>(src, (lay_blk * (size_t)a.Nc + (size_t)pos) * (size_t)a.gbw + lay_in);
+    const double k = (double)vc_dm_count<U16>(src, vc_dm_count_index(lay_blk, a.Nc, pos, a.gbw, lay_in));
     s1 += k;
     s2 += k * k;
     s0 += k == 0.0 ? 1.0 : 0.0;
@@ -193,7 +144,7 @@ __global__ __launch_bounds__(64) void vc_ppc_observed_cell_kernel(const VcPpcArg
   const int pos = a.cell_pos ? a.cell_pos[c] : c;
   double s = 0.0;
   for (int g = 0; g < a.Ng; ++g)
-    s += ppc_count<U16>(src, ((size_t)(g / a.gbw) * (size_t)a.Nc + (size_t)pos) * (size_t)a.gbw + (size_t)(g % a.gbw));
+    s += (double)vc_dm_count<U16>(src, vc_dm_count_index((size_t)(g / a.gbw), a.Nc, pos, a.gbw, (size_t)(g % a.gbw)));
   a.cell_obs[(size_t)m * a.Nc + c] = s;
 }
 

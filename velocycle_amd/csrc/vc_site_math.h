@@ -3,8 +3,9 @@
 // (reparameterised draws), their log q terms, prior log-densities and the chain rule from K_main's reduced sums to the
 // parameter gradients.  Every function works on values the caller has already loaded and returns results: none reads or
 // writes a buffer, so each kernel keeps its own load schedule.
-// Included by those three translation units only, after their `#pragma clang fp contract(off)`: the same statement gives
-// the same bits in every kernel it is inlined into.  The likelihood kernels (vc_main_*.hip) do not see this header.
+// Included by those three translation units, and for vc_harmonics by vc_draw_model.h (the consumers of posterior draws), after
+// their `#pragma clang fp contract(off)`: the same statement gives the same bits in every kernel it is inlined into.  The
+// likelihood kernels (vc_main_*.hip) do not see this header.
 // Reference: velocity_inference_guide.py:9-141, phase_inference_guide.py:10-56, the priors of
 // velocity_inference_model.py:322-353,383 / phase_inference_model.py:360-366,392.
 #pragma once

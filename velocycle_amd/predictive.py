@@ -61,12 +61,24 @@ class PredictiveDensity:
         return -2.0 * self.elpd_waic
 
 
-def check_request(noisemodel: str, n_draws: int, Ng: int, Nc: int, n_matrices: int, return_pointwise: bool):
-    """The refusals that need no device: raised before any library or GPU call."""
+def _check_noisemodel(fn: str, noisemodel: str):
+    """The noise models the draw kernels (csrc/vc_draw_model.h) cover, for pointwise_density and predictive_check (`fn`)."""
     if noisemodel == "Lognormal":
-        raise NotImplementedError("pointwise_density: Lognormal noise is not supported (NegativeBinomial or Poisson)")
+        raise NotImplementedError(f"{fn}: Lognormal noise is not supported (NegativeBinomial or Poisson)")
     if noisemodel not in ("NegativeBinomial", "Poisson"):
         raise ValueError(f"{noisemodel} not allowed")
+
+
+def _check_fast_set(fn: str, engine):
+    sp = engine.spec
+    if engine.stats["generic"]:
+        raise NotImplementedError(f"{fn}: this engine runs the run-time-sized kernel set (H = {sp.H}, Hw = {sp.Hw}, Nb = {sp.Nb}): "
+                                  "only what the compiled fast set covers is supported")
+
+
+def check_request(noisemodel: str, n_draws: int, Ng: int, Nc: int, n_matrices: int, return_pointwise: bool):
+    """The refusals that need no device: raised before any library or GPU call."""
+    _check_noisemodel("pointwise_density", noisemodel)
     if int(n_draws) < 2:
         raise ValueError(f"pointwise_density needs at least 2 draws (the variance over draws divides by n - 1), got {n_draws}")
     if return_pointwise and 4 * int(Ng) * int(Nc) * int(n_matrices) > MAX_POINTWISE_BYTES:
@@ -139,9 +151,7 @@ def pointwise_density(engine, draws: Dict[str, torch.Tensor], *, return_pointwis
     D = _draw_count(draws)
     Ng, Nc = sp.Ng, engine.Nc_local
     check_request(sp.noisemodel, D, Ng, Nc, len(mats), return_pointwise)
-    if engine.stats["generic"]:
-        raise NotImplementedError(f"pointwise_density: this engine runs the run-time-sized kernel set (H = {sp.H}, Hw = {sp.Hw}, Nb = {sp.Nb}): "
-                                  "only what the compiled fast set covers is supported")
+    _check_fast_set("pointwise_density", engine)
     dev = engine.device
     ptr, stride, keep = _device_draws(engine, draws, D)
     nq = 3 * len(mats)
@@ -267,10 +277,7 @@ class PredictiveCheck:
 
 def check_ppc_request(noisemodel: str, n_draws: int, Ng: int, Nc: int, n_matrices: int, keep_replicates: int):
     """The refusals of predictive_check that need no device: raised before any library or GPU call."""
-    if noisemodel == "Lognormal":
-        raise NotImplementedError("predictive_check: Lognormal noise is not supported (NegativeBinomial or Poisson)")
-    if noisemodel not in ("NegativeBinomial", "Poisson"):
-        raise ValueError(f"{noisemodel} not allowed")
+    _check_noisemodel("predictive_check", noisemodel)
     if int(n_draws) < 1:
         raise ValueError(f"predictive_check needs at least 1 draw, got {n_draws}")
     if not 0 <= int(keep_replicates) <= int(n_draws):
@@ -293,9 +300,7 @@ def predictive_check(engine, draws: Dict[str, torch.Tensor], *, seed: int, keep_
     Ng, Nc = sp.Ng, engine.Nc_local
     n_keep = int(keep_replicates)
     check_ppc_request(sp.noisemodel, D, Ng, Nc, len(mats), n_keep)
-    if engine.stats["generic"]:
-        raise NotImplementedError(f"predictive_check: this engine runs the run-time-sized kernel set (H = {sp.H}, Hw = {sp.Hw}, Nb = {sp.Nb}): "
-                                  "only what the compiled fast set covers is supported")
+    _check_fast_set("predictive_check", engine)
     dev = engine.device
     ptr, stride, keep = _device_draws(engine, draws, D)
     nm = len(mats)
