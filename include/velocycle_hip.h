@@ -45,6 +45,9 @@
  *   vc_predictive_check         Predictive(model, guide=guide, num_samples=n) with the observations removed
  *                               (the call pattern of velocity_inference_model.py:189-291 on the model of :338-386): replicated
  *                               counts per draw, reduced to statistics per gene and per cell
+ *   vc_predictive_pit           no counterpart (Predictive + a [D][Ng][Nc] CDF tensor per matrix would be it): the randomized
+ *                               probability integral transform of every observed count under the posterior predictive
+ *                               distribution of the model of velocity_inference_model.py:338-386 / phase_inference_model.py:343-395
  */
 #ifndef VELOCYCLE_HIP_H
 #define VELOCYCLE_HIP_H
@@ -589,6 +592,38 @@ int vc_predictive_check(vc_engine* e, int64_t n_draws, const float* phixy, int64
                         int64_t logbeta_stride, const float* nuomega, int64_t nuomega_stride, uint64_t seed, int64_t cell_begin,
                         int64_t cell_count, int64_t draw_begin, int64_t draw_count, int64_t* gene_rep_dev, int64_t* cell_rep_dev,
                         double* gene_obs_dev, double* cell_obs_dev, int32_t* keep_dev, int64_t n_keep, void* hip_stream);
+
+/* --- predictive PIT: randomized quantile residuals of every observed count over posterior draws ------------------------------
+ * No counterpart in the reference (Predictive plus a [D][Ng][Nc] CDF tensor per matrix would be it); the likelihood is the one of
+ * velocity_inference_model.py:338-386, phase_inference_model.py:343-395.  For count matrix m (S; velocity: S then U), gene g, cell c
+ * with the observed integer count k, under the draws theta_d:
+ *   F_lo = (1/D) sum_d P(K <= k - 1 | theta_d)      F_hi = (1/D) sum_d P(K <= k | theta_d)      u = F_lo + v (F_hi - F_lo)
+ * K ~ Poisson(mu) or GammaPoisson(r, r / mu), r = 1 / shape_inv[g], mu = exp(eta_S | eta_U) of vc_pointwise_density; v is the uniform
+ * of word 0 of the Philox4x32-10 block of vc_sample_counts at index g << 32 | (cell_offset + c), draw 0, matrix m, stage 2 (stages 0
+ * and 1 are the sampler's gamma and Poisson variates), attempt 0.  u is one float32 fma, clamped to [0, 1); its bin is
+ * min(n_bins - 1, floor(u n_bins)).  u is a pure function of (seed, m, g, global cell) and the draws (Dunn & Smyth 1996): uniform under
+ * a calibrated fit, U-shaped histograms under an under-dispersed model, hump-shaped under an over-dispersed one, skewed under bias.
+ * Draw pointers and strides as vc_pointwise_density (n_draws >= 1 here).  Outputs (DEVICE):
+ *   gene_hist_dev int64[nmat][Ng][n_bins]        bins of u over the cells [cell_begin, cell_begin + cell_count), ADDED to what the buffer
+ *                                                holds: zero it before the first call over a set of cells
+ *   cell_hist_dev int64[nmat][Nc_local][n_bins]  bins of u over the genes, written for the cells of the call
+ *   dense_dev     NULL, or float[nmat][3][Ng][Nc_local]: F_lo, F_hi and u per element, written for the cells of the call
+ * The CDF is the lower tail summed downward from k relative to pmf(k), rescaled so that no count of the upper tail overflows; every
+ * element comes out with 0 <= F_lo <= F_hi <= 1.  The loop is at most k long (it stops past the mode once the geometric bound of the
+ * remaining terms is below 2^-26 of the sum).  All sums are integers (LDS and 64-bit global integer atomics): identical bits under any cutting of the cells into calls
+ * (no alignment is asked of cell_begin), uint16 or float32 count storage, interleaved batches and repetition.  Workspace: the
+ * histogram tables of vc_pointwise_density (one float64 per distinct (gene, count) pair), shared with it.  Asynchronous on hip_stream;
+ * one call at a time per engine.  Supported: what vc_pointwise_density supports, COUNTS THAT ARE INTEGERS BELOW 2^24 (float32 holds every
+ * integer only up to there), rates that are finite, shape_inv < 2^30, n_bins in [2, 64].  VC_ERR_UNSUPPORTED (with the reason in
+ * vc_last_error) for Lognormal noise, the run-time-sized configurations and an engine that holds non-integer counts (they have no CDF
+ * on the integers) or a count of 2^24 or more; VC_ERR_ARG for a NULL engine (message: vc_last_error(NULL)),
+ * n_draws < 1, n_bins out of range, a NULL table or input, a stride or cell range out of bounds; VC_ERR_STATE before vc_finalize: all
+ * decided before anything is launched. */
+int vc_predictive_pit(vc_engine* e, int64_t n_draws, const float* phixy, int64_t phixy_stride, const float* nu, int64_t nu_stride,
+                      const float* dnu, const float* shape_inv, const float* loggamma, int64_t loggamma_stride, const float* logbeta,
+                      int64_t logbeta_stride, const float* nuomega, int64_t nuomega_stride, uint64_t seed, int32_t n_bins,
+                      int64_t cell_begin, int64_t cell_count, int64_t* gene_hist_dev, int64_t* cell_hist_dev, float* dense_dev,
+                      void* hip_stream);
 
 /* introspection ----------------------------------------------------------------------------- */
 /* Copies the value a site took in the last vc_elbo_grad to host memory (synchronises the stream). */

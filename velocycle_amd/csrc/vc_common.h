@@ -1060,6 +1060,20 @@ struct VcPpcArgs : VcDrawArgs {
 };
 int vc_launch_ppc(const VcPpcArgs& a, int H, bool vel, bool nb, int d_end, hipStream_t st);
 void vc_launch_ppc_observed(const VcPpcArgs& a, int nmat, hipStream_t st);
+// predictive PIT of every observed count (vc_pit.hip): what one launch reads and writes
+struct VcPitArgs : VcDrawArgs {
+  const int* h_ptr;                   // histogram CSR [2 Ng + 1], its count values and lgamma constants (as VcPwArgs)
+  const float* h_val;
+  const double* h_lgc;
+  int n_draws;
+  int n_bins;                         // 2 .. 64
+  uint64_t seed;                      // Philox key of the uniform v (stage 2 of the count sampler's stream)
+  long long cell_offset;              // global index of local cell 0
+  unsigned long long* gene_hist;      // [nmat][Ng][n_bins]  bins of u over the launch's cells: 64-bit integer atomics, ADDED
+  unsigned long long* cell_hist;      // [nmat][Nc][n_bins]  bins of u over the genes, written for the launch's cells
+  float* dense;                       // [nmat][3][Ng][Nc] (F_lo, F_hi, u) per element, or nullptr
+};
+int vc_launch_pit(const VcPitArgs& a, int H, bool vel, int noise, hipStream_t st);
 void vc_launch_pre(const VcDims& d, const VcBufs& b, const float* params, const float* eps,
                    uint64_t seed, long long step, const long long* step_dev, int cond_only, int with_hist,
                    hipStream_t st, int particles = 1, int particle = 0);

@@ -141,6 +141,9 @@ struct vc_engine {
   float* pw_val = nullptr;
   double* pw_lgc = nullptr;
   double* pw_ws = nullptr;
+  bool pit_checked = false, pit_bad = false;   // vc_predictive_pit: are all counts integers below 2^24 (decided at its first call)?
+  float pit_bad_value = 0.f;
+  bool pw_tables_made = false;          // pw_val / pw_lgc exist (vc_pointwise_density or vc_predictive_pit, whichever came first)
   // what the last vc_finalize measured about its own set-up
   std::vector<int> h_ptr_host;          // the histogram CSR as uploaded (vc_get_histogram)
   std::vector<float> h_val_host, h_cnt_host;
@@ -1990,7 +1993,7 @@ extern "C" int vc_expected_logs(vc_engine* e, const float* nu, const float* dnu,
 // workgroups (64 cells each) per launch of vc_pointwise_density: bounds its only workspace, [PW_MAX_SUPER][3 nmat][Ng] doubles
 static const int PW_MAX_SUPER = 512;
 
-// What vc_pointwise_density and vc_predictive_check (`fn`) share once their own arguments are checked: the refusals of a model or a
+// What vc_pointwise_density, vc_predictive_check and vc_predictive_pit (`fn`) share once their own arguments are checked: the refusals of a model or a
 // set of draws that the draw kernels (vc_draw_model.h) do not cover, then everything of `a` but the cell range.  reads_U: the call
 // reads the engine's unspliced counts when the model has them.
 static int draw_args(vc_engine* e, const char* fn, bool reads_U, const float* phixy, int64_t phixy_stride, const float* nu, int64_t nu_stride,
@@ -2021,6 +2024,21 @@ static int draw_args(vc_engine* e, const char* fn, bool reads_U, const float* ph
   return VC_OK;
 }
 
+// The histogram tables of the kernels that score observed counts (vc_pointwise_density, vc_predictive_pit), made at the first such
+// call: the count values in ascending order within every gene and room for their lgamma constants
+static int pw_tables(vc_engine* e) {
+  if (e->pw_tables_made) return VC_OK;
+  // (the dense bins come first, then the overflow list: ascending each, not together when a matrix holds non-integer counts)
+  std::vector<float> sorted = e->h_val_host;
+  const std::vector<int>& ptr = e->h_ptr_host;
+  for (size_t j = 0; j + 1 < ptr.size(); ++j) std::sort(sorted.begin() + ptr[j], sorted.begin() + ptr[j + 1]);
+  TRY(e->dalloc(&e->pw_val, sorted.size()));
+  if (!sorted.empty()) HIPCHK(e, hipMemcpy(e->pw_val, sorted.data(), sorted.size() * sizeof(float), hipMemcpyHostToDevice));
+  TRY(e->dalloc(&e->pw_lgc, sorted.size()));
+  e->pw_tables_made = true;
+  return VC_OK;
+}
+
 extern "C" int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* phixy, int64_t phixy_stride, const float* nu,
                                     int64_t nu_stride, const float* dnu, const float* shape_inv, const float* loggamma,
                                     int64_t loggamma_stride, const float* logbeta, int64_t logbeta_stride, const float* nuomega,
@@ -2044,15 +2062,8 @@ extern "C" int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* 
   hipStream_t st = (hipStream_t)hip_stream;
   const int nmat = vel ? 2 : 1, NQ = 3 * nmat;
   const int n_entries = (int)e->h_val_host.size();
+  TRY(pw_tables(e));
   if (!e->pw_ws) {
-    // the histogram values in ascending order within every gene (the dense bins come first, then the overflow list: ascending
-    // each, not together when a matrix holds non-integer counts)
-    std::vector<float> sorted = e->h_val_host;
-    const std::vector<int>& ptr = e->h_ptr_host;
-    for (size_t j = 0; j + 1 < ptr.size(); ++j) std::sort(sorted.begin() + ptr[j], sorted.begin() + ptr[j + 1]);
-    TRY(e->dalloc(&e->pw_val, sorted.size()));
-    if (!sorted.empty()) HIPCHK(e, hipMemcpy(e->pw_val, sorted.data(), sorted.size() * sizeof(float), hipMemcpyHostToDevice));
-    TRY(e->dalloc(&e->pw_lgc, sorted.size()));
     const size_t supers = (size_t)std::min<long long>(PW_MAX_SUPER, ((long long)d.Nc + 63) / 64);
     TRY(e->dalloc(&e->pw_ws, supers * NQ * (size_t)d.Ng));
   }
@@ -2123,6 +2134,57 @@ extern "C" int vc_predictive_check(vc_engine* e, int64_t n_draws, const float* p
     return e->fail(VC_ERR_RANGE, "vc_predictive_check: %lld replicate(s) outside the count sampler's range (rate not finite or above 2^20, "
                    "shape_inv <= 0, or a rejection loop out of attempts) since the last vc_clear_status; the tables of this call are not valid",
                    bad);
+  return VC_OK;
+  VC_GUARD_END(e)
+}
+
+extern "C" int vc_predictive_pit(vc_engine* e, int64_t n_draws, const float* phixy, int64_t phixy_stride, const float* nu,
+                                 int64_t nu_stride, const float* dnu, const float* shape_inv, const float* loggamma,
+                                 int64_t loggamma_stride, const float* logbeta, int64_t logbeta_stride, const float* nuomega,
+                                 int64_t nuomega_stride, uint64_t seed, int32_t n_bins, int64_t cell_begin, int64_t cell_count,
+                                 int64_t* gene_hist_dev, int64_t* cell_hist_dev, float* dense_dev, void* hip_stream) {
+  if (!e) { vc_set_global_error("vc_predictive_pit: null engine"); return VC_ERR_ARG; }
+  VC_GUARD_BEGIN
+  if (n_draws < 1) return e->fail(VC_ERR_ARG, "vc_predictive_pit: n_draws must be >= 1");
+  if (n_draws > (1 << 20)) return e->fail(VC_ERR_ARG, "vc_predictive_pit: more than 2^20 draws");
+  if (n_bins < 2 || n_bins > 64) return e->fail(VC_ERR_ARG, "vc_predictive_pit: n_bins must lie in [2, 64], got %d", (int)n_bins);
+  if (!gene_hist_dev || !cell_hist_dev) return e->fail(VC_ERR_ARG, "vc_predictive_pit: null gene_hist_dev / cell_hist_dev");
+  if (!e->finalized) return e->fail(VC_ERR_STATE, "vc_predictive_pit before vc_finalize");
+  const VcDims& d = e->d;
+  const VcBufs& b = e->b;
+  const bool vel = d.model == VC_MODEL_VELOCITY;
+  VcPitArgs a{};
+  TRY(draw_args(e, "vc_predictive_pit", true, phixy, phixy_stride, nu, nu_stride, dnu, shape_inv, loggamma, loggamma_stride, logbeta,
+                logbeta_stride, nuomega, nuomega_stride, a));
+  if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > d.Nc)
+    return e->fail(VC_ERR_ARG, "vc_predictive_pit: cells [%lld, %lld) must lie in [0, %d)", (long long)cell_begin,
+                   (long long)(cell_begin + cell_count), d.Nc);
+  // a count that is no integer has no CDF to evaluate, one from 2^24 on no float32 recurrence: a property of the finalized engine,
+  // decided once on the host's copy of the histogram values (vc_pit_count_ok)
+  if (!e->pit_checked) {
+    e->pit_checked = true;
+    e->pit_bad = false;
+    for (float v : e->h_val_host)
+      if (!vc_pit_count_ok(v)) { e->pit_bad = true; e->pit_bad_value = v; break; }
+  }
+  if (e->pit_bad) {
+    const float v = e->pit_bad_value;
+    if (v >= 0.f && v <= 3.0e38f && v != floorf(v))
+      return e->fail(VC_ERR_UNSUPPORTED, "vc_predictive_pit: the engine holds non-integer counts (%g): the CDF of a count model is "
+                     "defined on the integers only", (double)v);
+    return e->fail(VC_ERR_UNSUPPORTED, "vc_predictive_pit: the engine holds a count outside [0, 2^24) (%g): float32 holds every integer "
+                   "only below 2^24", (double)v);
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  TRY(pw_tables(e));
+  vc_launch_pw_const((int)e->h_val_host.size(), d.Ng, 2, b.h_ptr, e->pw_val, shape_inv, d.noise, e->pw_lgc, st);
+  a.h_ptr = b.h_ptr; a.h_val = e->pw_val; a.h_lgc = e->pw_lgc;
+  a.n_draws = (int)n_draws; a.n_bins = (int)n_bins; a.seed = seed; a.cell_offset = d.cell_offset;
+  a.c_begin = (int)cell_begin; a.c_end = (int)(cell_begin + cell_count);
+  a.gene_hist = (unsigned long long*)gene_hist_dev; a.cell_hist = (unsigned long long*)cell_hist_dev; a.dense = dense_dev;
+  if (vc_launch_pit(a, d.H, vel, d.noise, st) != VC_OK) return e->fail(VC_ERR_UNSUPPORTED, "vc_predictive_pit: no kernel for H = %d", d.H);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return e->fail(VC_ERR_HIP, "vc_predictive_pit: %s", hipGetErrorString(err));
   return VC_OK;
   VC_GUARD_END(e)
 }

@@ -20,6 +20,9 @@
 
 // a count the negative binomial / Poisson likelihood accepts: finite and >= 0
 static inline bool vc_count_ok(float v) { return v >= 0.f && v <= 3.0e38f; }
+// a count the predictive PIT (vc_predictive_pit) can score: an integer in [0, 2^24).  A count model has no CDF off the integers, and
+// from 2^24 on float32 no longer holds every integer (k - 1 may round back to k), so neither the recurrence nor its length is defined
+static inline bool vc_pit_count_ok(float v) { return v >= 0.f && v < 16777216.f && (float)(int)v == v; }
 // does the value own a dense bin?  (no float -> int conversion of an out-of-range value: that is undefined behaviour)
 static inline bool vc_count_dense(float v) { return v > 0.f && v < (float)VC_HIST_CAP && (float)(int)v == v; }
 

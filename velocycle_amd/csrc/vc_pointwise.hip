@@ -25,6 +25,7 @@
 // operations of a full one.
 #pragma clang fp contract(off)
 #include "vc_draw_model.h"      // eta_S / eta_U of one (draw, gene, cell) and the count access, shared with vc_ppc.hip
+#include "vc_pw_lik.h"          // pw_lik / pw_const: the log2 bracket and its lgamma constant, shared with vc_pit.hip
 
 namespace {
 
@@ -33,17 +34,6 @@ constexpr double PW_LN2 = 0.693147180559945309417;
 
 __device__ __forceinline__ float pw_rl(float v, int lane) {      // lane `lane` (compile-time) of v as a wave-uniform value
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-
-// log-probability / ln 2 without its lgamma constant.  eta2 = eta log2 e;  NB: r log2 r + k eta2 - (r + k) log2(r + mu)
-template <int NOISE>
-__device__ __forceinline__ float pw_lik(float k, float eta2, float r, float rl2) {
-  const float mu = __builtin_amdgcn_exp2f(eta2);
-  if (NOISE == VC_NOISE_NB) {
-    const float L = __builtin_amdgcn_logf(r + mu);
-    return __builtin_fmaf(-(r + k), L, __builtin_fmaf(k, eta2, rl2));
-  }
-  return __builtin_fmaf(k, eta2, -(mu * VC_LOG2E));
 }
 
 struct PwState { float l0, m, s, mean, m2; };
@@ -58,19 +48,6 @@ __device__ __forceinline__ void pw_update(PwState& q, float l, bool first, float
   const float del = t - q.mean;
   q.mean = __builtin_fmaf(del, inv_n, q.mean);
   q.m2 = __builtin_fmaf(del, t - q.mean, q.m2);
-}
-
-// the lgamma constant of (matrix, gene, count): the histogram entry of that count (values ascending within a gene)
-__device__ __forceinline__ double pw_const(const VcPwArgs& a, int mat, int g, float k) {
-  if (k == 0.f) return 0.0;
-  int lo = a.h_ptr[(size_t)mat * a.Ng + g], hi = a.h_ptr[(size_t)mat * a.Ng + g + 1];
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    const float v = a.h_val[mid];
-    if (v == k) return a.h_lgc[mid];
-    if (v < k) lo = mid + 1; else hi = mid;
-  }
-  return __builtin_nan("");                  // a count the histogram does not list: cannot happen on a finalized engine
 }
 
 // KIND 0: phase model (S) | 1: velocity (S and U per draw) | 2: velocity, everything eta_S depends on is the same in every draw

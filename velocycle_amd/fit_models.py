@@ -457,6 +457,40 @@ class _FitBase:
             c0 += nc_r
         return P.merge_check_shards(parts)
 
+    def predictive_pit(self, num_samples=None, seed=None, draws=None, bins=20, return_pointwise=False):
+        """Randomized probability integral transform of every observed count under the fitted model's posterior predictive
+        distribution (not in the reference; Dunn-Smyth quantile residuals), as a `velocycle_amd.predictive.PredictivePIT`: histograms
+        of u per gene and per cell with their chi-square summaries against uniform, and on request F_lo, F_hi and u per element.
+        num_samples / seed / draws as `posterior_predictive_check`; `seed` also keys the randomization.  Cells sharded over ranks:
+        every rank transforms its cells, the records are gathered and merged (`predictive.merge_pit_shards`)."""
+        from . import predictive as P
+        if self.engine is None or getattr(self, "losses", None) is None:
+            raise ValueError("predictive_pit: the model has not been fitted (call fit() first)")
+        sp = self.spec
+        n = int(self.num_samples if num_samples is None else num_samples) if draws is None else P._draw_count(draws)
+        nmat = 2 if sp.kind == "velocity" else 1
+        P.check_pit_request(sp.noisemodel, n, bins, sp.Ng, self.engine.Nc_local, nmat, return_pointwise)
+        eng = self.engine
+        base = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if seed is None else int(seed)
+        base = broadcast_int(base, self._pg, eng.device)
+        if draws is None:
+            names = [k for k in ("ν", "Δν", "ϕxy", "shape_inv", "logγg", "logβg", "νω") if self._site_exists(k)]
+            draws = eng.sample_posterior(names, n, seed=base, step0=0)
+        rec = P.predictive_pit(eng, draws, seed=base, bins=bins, return_pointwise=return_pointwise)
+        if self._world == 1:
+            return rec
+        mats, dev = list(rec.cell_hist), eng.device
+        cell = self._gather(torch.stack([rec.cell_hist[m] for m in mats]).to(dev), 1)
+        gene = self._gather_ranks(torch.stack([rec.gene_hist[m] for m in mats]))
+        pw = self._gather(torch.stack([rec.pointwise[m] for m in mats]).to(dev), 3) if rec.pointwise is not None else None
+        parts, c0 = [], 0
+        for r, nc_r in enumerate(self._shard_sizes):
+            pick = lambda src: {m: src[i].clone() for i, m in enumerate(mats)}
+            parts.append(P.PredictivePIT(gene_hist=pick(gene[r]), cell_hist=pick(cell[:, c0:c0 + nc_r]), n_draws=rec.n_draws, bins=rec.bins,
+                                         seed=rec.seed, pointwise=None if pw is None else pick(pw[:, :, :, c0:c0 + nc_r])))
+            c0 += nc_r
+        return P.merge_pit_shards(parts)
+
     def _gather_ranks(self, local: torch.Tensor) -> torch.Tensor:
         """(world, *local.shape): every rank's copy of a replicated-shape tensor, in rank order."""
         return gather_cells(local.unsqueeze(0).to(self.engine.device), 0, [1] * self._world, self._pg)

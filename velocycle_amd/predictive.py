@@ -385,3 +385,118 @@ def sample_counts(eta: torch.Tensor, shape_inv: Optional[torch.Tensor] = None, *
             raise _lib.CountSamplerRangeError(msg)
         raise (ValueError if rc == _lib.VC_ERR_ARG else RuntimeError)(msg)
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# predictive PIT: randomized quantile residuals of every observed count over posterior draws (vc_predictive_pit, csrc/vc_pit.hip)
+# ----------------------------------------------------------------------------------------------------------------------------------
+PIT_MIN_BINS, PIT_MAX_BINS = 2, 64
+
+
+def _uniformity(hist):
+    """Float64 summaries of integer histograms (..., B) against the uniform distribution: Pearson's chi-square with the expected count
+    n / B per bin (n: the row's total), its z-score (chi2 - (B - 1)) / sqrt(2 (B - 1)) and the share of the two edge bins (2 / B when
+    uniform).  A row without elements gives NaN."""
+    h = hist.double()
+    B = h.shape[-1]
+    n = h.sum(-1)
+    expected = (n / B).unsqueeze(-1)
+    chi2 = (((h - expected) ** 2) / expected).sum(-1)
+    return {"chi2": chi2, "z": (chi2 - (B - 1)) / math.sqrt(2.0 * (B - 1)), "edge_share": (h[..., 0] + h[..., -1]) / n}
+
+
+@dataclass
+class PredictivePIT:
+    """Randomized PIT values u of every observed count under the posterior predictive distribution, binned, per count matrix
+    {"S": ..., "U": ...}, CPU tensors.  Calibrated: u uniform; U-shaped histograms: the model is under-dispersed; hump-shaped:
+    over-dispersed; skewed: biased.
+
+    gene_hist[m]  (Ng, bins) int64: per gene, the bins of u over the record's cells
+    cell_hist[m]  (Nc, bins) int64: per cell, the bins of u over the genes
+    pointwise[m]  (3, Ng, Nc) float32: F_lo = P(K <= k - 1), F_hi = P(K <= k) and u = F_lo + v (F_hi - F_lo) per element, when asked for
+    Derived on the host in float64: `gene()`, `cell()`, `pooled()` -- chi-square against uniform, its z-score and the edge-bin share."""
+    gene_hist: Dict[str, torch.Tensor]
+    cell_hist: Dict[str, torch.Tensor]
+    n_draws: int
+    bins: int
+    seed: int
+    pointwise: Optional[Dict[str, torch.Tensor]] = None
+
+    def gene(self):
+        """{matrix: {"chi2", "z", "edge_share": (Ng,) float64}}."""
+        return {m: _uniformity(h) for m, h in self.gene_hist.items()}
+
+    def cell(self):
+        """{matrix: {"chi2", "z", "edge_share": (Nc,) float64}}."""
+        return {m: _uniformity(h) for m, h in self.cell_hist.items()}
+
+    def pooled(self):
+        """{matrix: {"hist": (bins,) int64, "chi2", "z", "edge_share": float}} over all elements of the matrix."""
+        out = {}
+        for m, h in self.gene_hist.items():
+            tot = h.sum(0)
+            out[m] = {"hist": tot, **{k: float(v) for k, v in _uniformity(tot).items()}}
+        return out
+
+
+def check_pit_request(noisemodel: str, n_draws: int, bins: int, Ng: int, Nc: int, n_matrices: int, return_pointwise: bool):
+    """The refusals of predictive_pit that need no device: raised before any library or GPU call."""
+    _check_noisemodel("predictive_pit", noisemodel)
+    if int(n_draws) < 1:
+        raise ValueError(f"predictive_pit needs at least 1 draw, got {n_draws}")
+    if not PIT_MIN_BINS <= int(bins) <= PIT_MAX_BINS:
+        raise ValueError(f"predictive_pit: bins must lie in [{PIT_MIN_BINS}, {PIT_MAX_BINS}], got {bins}")
+    if return_pointwise and 12 * int(Ng) * int(Nc) * int(n_matrices) > MAX_POINTWISE_BYTES:
+        raise ValueError(f"return_pointwise: F_lo, F_hi and u of {n_matrices} x {Ng} x {Nc} elements exceed {MAX_POINTWISE_BYTES} bytes; "
+                         "use the per-gene / per-cell histograms")
+
+
+def predictive_pit(engine, draws: Dict[str, torch.Tensor], *, seed: int, bins: int = 20, return_pointwise: bool = False,
+                   chunk_cells: Optional[int] = None) -> PredictivePIT:
+    """The randomized PIT of every observed count of this engine's cells under explicit draws (as `pointwise_density` takes them):
+    histograms of u per gene and per cell, and on request F_lo, F_hi and u per element.  Nothing of size D x Ng x Nc exists.
+    seed: Philox key of the randomization; u depends on (seed, matrix, gene, global cell) and the draws alone.
+    chunk_cells: cells per library call (default: all); the result does not depend on it.  There is no CPU path."""
+    sp = engine.spec
+    vel = sp.kind == "velocity"
+    mats = ["S", "U"] if vel else ["S"]
+    D = _draw_count(draws)
+    Ng, Nc = sp.Ng, engine.Nc_local
+    B = int(bins)
+    check_pit_request(sp.noisemodel, D, B, Ng, Nc, len(mats), return_pointwise)
+    _check_fast_set("predictive_pit", engine)
+    dev = engine.device
+    ptr, stride, keep = _device_draws(engine, draws, D)
+    nm = len(mats)
+    gene = torch.zeros((nm, Ng, B), dtype=torch.int64, device=dev)
+    cell = torch.zeros((nm, Nc, B), dtype=torch.int64, device=dev)
+    dense = torch.empty((nm, 3, Ng, Nc), dtype=torch.float32, device=dev) if return_pointwise else None
+    step = Nc if not chunk_cells else max(1, int(chunk_cells))
+    g = lambda k: ptr.get(k)
+    for c0 in range(0, Nc, step):
+        engine._check(engine.lib.vc_predictive_pit(
+            engine._h, C.c_int64(D), g("ϕxy"), C.c_int64(stride["ϕxy"]), g("ν"), C.c_int64(stride["ν"]), g("Δν"), g("shape_inv"),
+            g("logγg"), C.c_int64(stride.get("logγg", 0)), g("logβg"), C.c_int64(stride.get("logβg", 0)), g("νω"),
+            C.c_int64(stride.get("νω", 0)), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_int32(B), C.c_int64(c0),
+            C.c_int64(min(step, Nc - c0)), C.c_void_p(gene.data_ptr()), C.c_void_p(cell.data_ptr()),
+            C.c_void_p(dense.data_ptr()) if dense is not None else None, engine._stream()))
+    torch.cuda.synchronize(dev)
+    del keep
+    pick = lambda t: {m: t[i].cpu().clone() for i, m in enumerate(mats)}
+    return PredictivePIT(gene_hist=pick(gene), cell_hist=pick(cell), n_draws=D, bins=B, seed=int(seed),
+                         pointwise=None if dense is None else pick(dense))
+
+
+def merge_pit_shards(parts) -> PredictivePIT:
+    """The records of the ranks of a cell-sharded evaluation, in rank order, as one record: the per-gene histograms added (integers:
+    exact), the per-cell histograms and the dense columns concatenated."""
+    parts = list(parts)
+    first = parts[0]
+    if any(p.n_draws != first.n_draws or p.seed != first.seed or p.bins != first.bins for p in parts):
+        raise ValueError("merge_pit_shards: the records come from different draws, seeds or bins")
+    if any((p.pointwise is None) != (first.pointwise is None) for p in parts):
+        raise ValueError("merge_pit_shards: only some of the records hold pointwise values")
+    gene = {m: torch.stack([p.gene_hist[m] for p in parts]).sum(0) for m in first.gene_hist}
+    cell = {m: torch.cat([p.cell_hist[m] for p in parts], dim=0) for m in first.cell_hist}
+    pw = None if first.pointwise is None else {m: torch.cat([p.pointwise[m] for p in parts], dim=2) for m in first.pointwise}
+    return PredictivePIT(gene_hist=gene, cell_hist=cell, n_draws=first.n_draws, bins=first.bins, seed=first.seed, pointwise=pw)
