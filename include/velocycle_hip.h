@@ -48,6 +48,10 @@
  *   vc_predictive_pit           no counterpart (Predictive + a [D][Ng][Nc] CDF tensor per matrix would be it): the randomized
  *                               probability integral transform of every observed count under the posterior predictive
  *                               distribution of the model of velocity_inference_model.py:338-386 / phase_inference_model.py:343-395
+ *   vc_phase_marginal           the Bayesian twin of Phases.from_cycle_mle (phases.py:471-509): on its grid of phases (:495) the
+ *                               likelihood of velocity_inference_model.py:338-386 / phase_inference_model.py:343-395 of every cell
+ *                               (both matrices, batch offsets, per-gene shape_inv, posterior draws), as the cell's phase posterior
+ *                               and its evidence with the phase integrated out
  */
 #ifndef VELOCYCLE_HIP_H
 #define VELOCYCLE_HIP_H
@@ -624,6 +628,41 @@ int vc_predictive_pit(vc_engine* e, int64_t n_draws, const float* phixy, int64_t
                       int64_t logbeta_stride, const float* nuomega, int64_t nuomega_stride, uint64_t seed, int32_t n_bins,
                       int64_t cell_begin, int64_t cell_count, int64_t* gene_hist_dev, int64_t* cell_hist_dev, float* dense_dev,
                       void* hip_stream);
+
+/* --- phase-marginal scoring: per-cell phase posterior and evidence on a grid of phases -------------------------------------------
+ * The Bayesian twin of Phases.from_cycle_mle (phases.py:471-509), which scores the spliced matrix at point estimates with one
+ * dispersion and keeps the arg-max bin.  Here, for cell c, draw d of the gene-level and global sites theta_d = (nu, dnu, shape_inv,
+ * loggamma, logbeta, nuomega) and grid phase phi_j = 2 pi j / n_bins (the grid of phases.py:495), with the likelihood of
+ * velocity_inference_model.py:338-386, phase_inference_model.py:343-395 (eta_S, eta_U, lgamma terms as vc_pointwise_density) evaluated
+ * with the cell's direction set to phi_j:
+ *   a[d,c,j]      = lw[c,j] + sum_matrices sum_g log p(k_gc | theta_d, phi_j)
+ *   evidence[c]   = log((1/D) sum_d sum_j exp a[d,c,j])             the cell's log predictive density with the phase integrated out
+ *   post[c,j]     = sum_d exp a[d,c,j] / sum_d sum_j' exp a[d,c,j']  the phase posterior on the grid (rows sum to 1)
+ *   per_draw[d,c] = log sum_j exp a[d,c,j]
+ * lw[c,j] is the log prior mass of bin j (sum_j exp lw = 1 is the caller's business): log_prior_dev float[Nc_local][n_bins], or NULL
+ * for the flat prior, whose lw is -log(n_bins) rounded to float32 (a table of that value gives the bits of NULL).  The engine holds
+ * the cells to be scored -- they need not be cells any fit has seen -- and no phixy is read.  Draw pointers and strides as
+ * vc_pointwise_density WITHOUT phixy; n_draws in [1, 2^20], n_bins in [2, 4096].  When nu_stride is 0 the spliced sums of a (cell, bin)
+ * are formed once instead of per draw, by the same statements: the bits do not depend on it.  Outputs (DEVICE, written for the cells
+ * [cell_begin, cell_begin + cell_count)):
+ *   evidence_dev  double[Nc_local]
+ *   post_dev      NULL, or float[Nc_local][n_bins]
+ *   per_draw_dev  NULL, or double[n_draws][Nc_local]
+ * One kernel (csrc/vc_phase_marginal.hip): lane = cell, float32 partial sums of 4 genes into float64 accumulators per (cell, bin),
+ * the lgamma constants summed once per cell in float64 from the histogram tables of vc_pointwise_density, an online log-sum-exp in
+ * float64 over bins and draws; no atomics.  Finite a, however negative, give finite outputs.  Identical bits under repetition, any
+ * cutting of the cells into calls (no alignment is asked of cell_begin), uint16 or float32 count storage, interleaved batches and
+ * sharding.  For the velocity model the integrand is not smooth in phi (the relu(z) + 1e-5 floor): the evidence is that of the
+ * discrete grid.  Workspace (engine-owned, allocated at the first call, again when a call needs more): the grid's sin / cos table,
+ * 32 n_bins bytes, and the bins' log masses of one launch, 8 n_bins min(cells of the call rounded up to 64, max(64, 2^23 / n_bins
+ * rounded down to 64)) bytes <= 64 MiB; a call of more cells is cut into launches.  Asynchronous on hip_stream; one call at a time
+ * per engine.  VC_ERR_UNSUPPORTED (with the reason in vc_last_error) for Lognormal noise and the run-time-sized configurations;
+ * VC_ERR_ARG for a NULL engine (message: vc_last_error(NULL)), n_draws or n_bins out of range, a NULL evidence_dev or input, a stride
+ * or cell range out of bounds; VC_ERR_STATE before vc_finalize: all decided before anything is launched. */
+int vc_phase_marginal(vc_engine* e, int64_t n_draws, const float* nu, int64_t nu_stride, const float* dnu, const float* shape_inv,
+                      const float* loggamma, int64_t loggamma_stride, const float* logbeta, int64_t logbeta_stride,
+                      const float* nuomega, int64_t nuomega_stride, int32_t n_bins, const float* log_prior_dev, int64_t cell_begin,
+                      int64_t cell_count, double* evidence_dev, float* post_dev, double* per_draw_dev, void* hip_stream);
 
 /* introspection ----------------------------------------------------------------------------- */
 /* Copies the value a site took in the last vc_elbo_grad to host memory (synchronises the stream). */

@@ -321,6 +321,17 @@ class Phases:
             self.set_phixy(xy)
         return (best, prof) if return_profile else None
 
+    @classmethod
+    def from_phase_marginal(cls, record, cell_names=None, concentration=None):
+        """Phases from a `velocycle_amd.predictive.PhaseMarginal`: ϕxy = kappa (cos, sin) of every cell's posterior circular mean.
+        kappa: `concentration` if given; otherwise, per cell, the kappa whose projected normal -- the angle of Normal(kappa u, I), which
+        is what the model makes of a ϕxy prior -- has the record's mean resultant length (a monotone 1-D inversion on the host)."""
+        from .predictive import concentration_of_resultant
+        mean = record.mean_phase.double().numpy()
+        kappa = np.full(mean.shape, float(concentration)) if concentration is not None else \
+            concentration_of_resultant(record.resultant_length).numpy()
+        return cls.from_array(np.vstack([np.cos(mean), np.sin(mean)]) * kappa, cell_names=cell_names)
+
     def shift_zero(self, gene=None, phase=None):
         if gene is not None:
             raise Exception("Error: must phase for desired shift")

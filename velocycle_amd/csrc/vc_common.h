@@ -1074,6 +1074,25 @@ struct VcPitArgs : VcDrawArgs {
   float* dense;                       // [nmat][3][Ng][Nc] (F_lo, F_hi, u) per element, or nullptr
 };
 int vc_launch_pit(const VcPitArgs& a, int H, bool vel, int noise, hipStream_t st);
+// phase-marginal scoring (vc_phase_marginal.hip): what one launch reads and writes (phixy of VcDrawArgs is not read)
+#define VC_PM_MAX_BINS 4096
+struct VcPmArgs : VcDrawArgs {
+  const int* h_ptr;                   // histogram CSR [2 Ng + 1], its count values and lgamma constants (as VcPwArgs)
+  const float* h_val;
+  const double* h_lgc;
+  int n_draws;
+  int n_bins;                         // 2 .. VC_PM_MAX_BINS
+  int s_once;                         // nothing the spliced term depends on varies over the draws: its sums are formed once per tile
+  float lw_flat;                      // -log(n_bins) rounded to float32: the log prior mass of a bin when log_prior is null
+  const float* grid;                  // [n_bins][8]: sin(k phi_j), k = 1..3, cos(k phi_j), k = 1..3, 0, 0; formed in float64 on the host
+  const float* log_prior;             // [Nc][n_bins] log prior mass of every bin, or nullptr: flat
+  double* ws;                         // [n_bins][ws_ld] log mass of every bin of the launch's cells (column: cell - c_begin)
+  long long ws_ld;                    // >= the launch's cells rounded up to 64
+  double* evidence;                   // [Nc]
+  float* post;                        // [Nc][n_bins], or nullptr
+  double* per_draw;                   // [n_draws][Nc], or nullptr
+};
+int vc_launch_phase_marginal(const VcPmArgs& a, int H, bool vel, int noise, hipStream_t st);
 void vc_launch_pre(const VcDims& d, const VcBufs& b, const float* params, const float* eps,
                    uint64_t seed, long long step, const long long* step_dev, int cond_only, int with_hist,
                    hipStream_t st, int particles = 1, int particle = 0);

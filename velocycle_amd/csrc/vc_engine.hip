@@ -144,6 +144,12 @@ struct vc_engine {
   bool pit_checked = false, pit_bad = false;   // vc_predictive_pit: are all counts integers below 2^24 (decided at its first call)?
   float pit_bad_value = 0.f;
   bool pw_tables_made = false;          // pw_val / pw_lgc exist (vc_pointwise_density or vc_predictive_pit, whichever came first)
+  // vc_phase_marginal (allocated at its first call, again when a call needs more): the grid's sin / cos table [pm_grid_bins][8] and the
+  // bins' log masses of one launch, pm_ws_len doubles
+  float* pm_grid = nullptr;
+  int pm_grid_bins = 0;
+  double* pm_ws = nullptr;
+  size_t pm_ws_len = 0;
   // what the last vc_finalize measured about its own set-up
   std::vector<int> h_ptr_host;          // the histogram CSR as uploaded (vc_get_histogram)
   std::vector<float> h_val_host, h_cnt_host;
@@ -1995,8 +2001,9 @@ static const int PW_MAX_SUPER = 512;
 
 // What vc_pointwise_density, vc_predictive_check and vc_predictive_pit (`fn`) share once their own arguments are checked: the refusals of a model or a
 // set of draws that the draw kernels (vc_draw_model.h) do not cover, then everything of `a` but the cell range.  reads_U: the call
-// reads the engine's unspliced counts when the model has them.
-static int draw_args(vc_engine* e, const char* fn, bool reads_U, const float* phixy, int64_t phixy_stride, const float* nu, int64_t nu_stride,
+// reads the engine's unspliced counts when the model has them.  reads_phixy: the call takes the cells' directions from the draws
+// (vc_phase_marginal does not: it walks a grid of phases).
+static int draw_args(vc_engine* e, const char* fn, bool reads_U, bool reads_phixy, const float* phixy, int64_t phixy_stride, const float* nu, int64_t nu_stride,
                      const float* dnu, const float* shape_inv, const float* loggamma, int64_t loggamma_stride, const float* logbeta,
                      int64_t logbeta_stride, const float* nuomega, int64_t nuomega_stride, VcDrawArgs& a) {
   const VcDims& d = e->d;
@@ -2008,13 +2015,13 @@ static int draw_args(vc_engine* e, const char* fn, bool reads_U, const float* ph
                    "%d angular-speed coefficients): only what the compiled fast set covers is supported", fn, d.H, d.Hw, d.Nb, d.R, d.NW);
   const bool vel = d.model == VC_MODEL_VELOCITY, nb = d.noise == VC_NOISE_NB;
   const int nbat = d.with_dnu ? d.Nb : 0;
-  if (!phixy || !nu) return e->fail(VC_ERR_ARG, "%s: null phixy / nu", fn);
+  if ((reads_phixy && !phixy) || !nu) return e->fail(VC_ERR_ARG, "%s: null phixy / nu", fn);
   if (nbat > 0 && !dnu) return e->fail(VC_ERR_ARG, "%s: the model has batch offsets, dnu is required", fn);
   if (nb && !shape_inv) return e->fail(VC_ERR_ARG, "%s: the negative binomial needs shape_inv", fn);
   if (vel && (!loggamma || !logbeta || !nuomega)) return e->fail(VC_ERR_ARG, "%s: null loggamma / logbeta / nuomega", fn);
   if (vel && reads_U && !b.U) return e->fail(VC_ERR_STATE, "%s: the engine holds no unspliced counts", fn);
   auto stride_ok = [](int64_t s, long long full) { return s == 0 || s == full; };
-  if (!stride_ok(phixy_stride, 2LL * d.Nc) || !stride_ok(nu_stride, (long long)d.Ng * d.Nh) ||
+  if ((reads_phixy && !stride_ok(phixy_stride, 2LL * d.Nc)) || !stride_ok(nu_stride, (long long)d.Ng * d.Nh) ||
       (vel && (!stride_ok(loggamma_stride, d.Ng) || !stride_ok(logbeta_stride, d.Ng) || !stride_ok(nuomega_stride, d.NW))))
     return e->fail(VC_ERR_ARG, "%s: a draw stride must be 0 or the length of its site", fn);
   a.S = b.S; a.U = b.U; a.cf = b.cf; a.Dm = b.Dm; a.Dbm = b.Dbm; a.cell_pos = b.cell_pos;
@@ -2054,7 +2061,7 @@ extern "C" int vc_pointwise_density(vc_engine* e, int64_t n_draws, const float* 
   const VcBufs& b = e->b;
   const bool vel = d.model == VC_MODEL_VELOCITY;
   VcPwArgs a{};
-  TRY(draw_args(e, "vc_pointwise_density", true, phixy, phixy_stride, nu, nu_stride, dnu, shape_inv, loggamma, loggamma_stride, logbeta,
+  TRY(draw_args(e, "vc_pointwise_density", true, true, phixy, phixy_stride, nu, nu_stride, dnu, shape_inv, loggamma, loggamma_stride, logbeta,
                 logbeta_stride, nuomega, nuomega_stride, a));
   if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > d.Nc || (cell_begin & 63))
     return e->fail(VC_ERR_ARG, "vc_pointwise_density: cells [%lld, %lld) must lie in [0, %d) and start at a multiple of 64",
@@ -2105,7 +2112,7 @@ extern "C" int vc_predictive_check(vc_engine* e, int64_t n_draws, const float* p
   const VcBufs& b = e->b;
   const bool vel = d.model == VC_MODEL_VELOCITY, nb = d.noise == VC_NOISE_NB;
   VcPpcArgs a{};
-  TRY(draw_args(e, "vc_predictive_check", gene_obs_dev != nullptr, phixy, phixy_stride, nu, nu_stride, dnu, shape_inv, loggamma,
+  TRY(draw_args(e, "vc_predictive_check", gene_obs_dev != nullptr, true, phixy, phixy_stride, nu, nu_stride, dnu, shape_inv, loggamma,
                 loggamma_stride, logbeta, logbeta_stride, nuomega, nuomega_stride, a));
   if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > d.Nc)
     return e->fail(VC_ERR_ARG, "vc_predictive_check: cells [%lld, %lld) must lie in [0, %d)", (long long)cell_begin,
@@ -2154,7 +2161,7 @@ extern "C" int vc_predictive_pit(vc_engine* e, int64_t n_draws, const float* phi
   const VcBufs& b = e->b;
   const bool vel = d.model == VC_MODEL_VELOCITY;
   VcPitArgs a{};
-  TRY(draw_args(e, "vc_predictive_pit", true, phixy, phixy_stride, nu, nu_stride, dnu, shape_inv, loggamma, loggamma_stride, logbeta,
+  TRY(draw_args(e, "vc_predictive_pit", true, true, phixy, phixy_stride, nu, nu_stride, dnu, shape_inv, loggamma, loggamma_stride, logbeta,
                 logbeta_stride, nuomega, nuomega_stride, a));
   if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > d.Nc)
     return e->fail(VC_ERR_ARG, "vc_predictive_pit: cells [%lld, %lld) must lie in [0, %d)", (long long)cell_begin,
@@ -2185,6 +2192,77 @@ extern "C" int vc_predictive_pit(vc_engine* e, int64_t n_draws, const float* phi
   if (vc_launch_pit(a, d.H, vel, d.noise, st) != VC_OK) return e->fail(VC_ERR_UNSUPPORTED, "vc_predictive_pit: no kernel for H = %d", d.H);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return e->fail(VC_ERR_HIP, "vc_predictive_pit: %s", hipGetErrorString(err));
+  return VC_OK;
+  VC_GUARD_END(e)
+}
+
+// bytes of the bins' log masses one launch of vc_phase_marginal may hold: bounds the cells of a launch (at least 64)
+static const size_t PM_WS_BYTES = 64u << 20;
+
+extern "C" int vc_phase_marginal(vc_engine* e, int64_t n_draws, const float* nu, int64_t nu_stride, const float* dnu, const float* shape_inv,
+                                 const float* loggamma, int64_t loggamma_stride, const float* logbeta, int64_t logbeta_stride,
+                                 const float* nuomega, int64_t nuomega_stride, int32_t n_bins, const float* log_prior_dev,
+                                 int64_t cell_begin, int64_t cell_count, double* evidence_dev, float* post_dev, double* per_draw_dev,
+                                 void* hip_stream) {
+  if (!e) { vc_set_global_error("vc_phase_marginal: null engine"); return VC_ERR_ARG; }
+  VC_GUARD_BEGIN
+  if (n_draws < 1) return e->fail(VC_ERR_ARG, "vc_phase_marginal: n_draws must be >= 1");
+  if (n_draws > (1 << 20)) return e->fail(VC_ERR_ARG, "vc_phase_marginal: more than 2^20 draws");
+  if (n_bins < 2 || n_bins > VC_PM_MAX_BINS) return e->fail(VC_ERR_ARG, "vc_phase_marginal: n_bins must lie in [2, 4096], got %d", (int)n_bins);
+  if (!evidence_dev) return e->fail(VC_ERR_ARG, "vc_phase_marginal: null evidence_dev");
+  if (!e->finalized) return e->fail(VC_ERR_STATE, "vc_phase_marginal before vc_finalize");
+  const VcDims& d = e->d;
+  const VcBufs& b = e->b;
+  const bool vel = d.model == VC_MODEL_VELOCITY;
+  VcPmArgs a{};
+  TRY(draw_args(e, "vc_phase_marginal", true, false, nullptr, 0, nu, nu_stride, dnu, shape_inv, loggamma, loggamma_stride, logbeta,
+                logbeta_stride, nuomega, nuomega_stride, a));
+  if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > d.Nc)
+    return e->fail(VC_ERR_ARG, "vc_phase_marginal: cells [%lld, %lld) must lie in [0, %d)", (long long)cell_begin,
+                   (long long)(cell_begin + cell_count), d.Nc);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int B = (int)n_bins;
+  // sin / cos of k phi_j, phi_j = 2 pi j / B (the grid of phases.py:495), in float64, rounded once
+  if (e->pm_grid_bins != B) {
+    std::vector<float> tab((size_t)B * 8, 0.f);
+    for (int j = 0; j < B; ++j) {
+      const double phi = 2.0 * 3.14159265358979323846 * (double)j / (double)B;
+      for (int k = 0; k < VC_MAXH; ++k) {
+        tab[(size_t)j * 8 + k] = (float)std::sin((double)(k + 1) * phi);
+        tab[(size_t)j * 8 + VC_MAXH + k] = (float)std::cos((double)(k + 1) * phi);
+      }
+    }
+    if (e->pm_grid) { e->dfree(e->pm_grid); e->pm_grid = nullptr; e->pm_grid_bins = 0; }
+    TRY(e->dalloc(&e->pm_grid, tab.size()));
+    HIPCHK(e, hipMemcpy(e->pm_grid, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    e->pm_grid_bins = B;
+  }
+  // cells per launch: the workspace [B][cells] of float64 stays within PM_WS_BYTES (B = 4096: 2 048 cells)
+  const long long cap = std::max<long long>(64, (long long)(PM_WS_BYTES / (8 * (size_t)B)) / 64 * 64);
+  const long long ld = std::min<long long>(cap, (cell_count + 63) / 64 * 64);
+  if (e->pm_ws_len < (size_t)B * (size_t)ld) {
+    if (e->pm_ws) { e->dfree(e->pm_ws); e->pm_ws = nullptr; e->pm_ws_len = 0; }
+    TRY(e->dalloc(&e->pm_ws, (size_t)B * (size_t)ld));
+    e->pm_ws_len = (size_t)B * (size_t)ld;
+  }
+  TRY(pw_tables(e));
+  vc_launch_pw_const((int)e->h_val_host.size(), d.Ng, 2, b.h_ptr, e->pw_val, shape_inv, d.noise, e->pw_lgc, st);
+  a.h_ptr = b.h_ptr; a.h_val = e->pw_val; a.h_lgc = e->pw_lgc;
+  a.n_draws = (int)n_draws; a.n_bins = B;
+  a.s_once = nu_stride == 0 ? 1 : 0;        // (dnu and shape_inv are single values)
+  a.lw_flat = (float)(-std::log((double)B));
+  a.grid = e->pm_grid; a.log_prior = log_prior_dev;
+  a.ws = e->pm_ws; a.ws_ld = ld;
+  a.evidence = evidence_dev; a.post = post_dev; a.per_draw = per_draw_dev;
+  const long long c_end = cell_begin + cell_count;
+  for (long long c0 = cell_begin; c0 < c_end; c0 += ld) {
+    a.c_begin = (int)c0;
+    a.c_end = (int)std::min<long long>(c_end, c0 + ld);
+    if (vc_launch_phase_marginal(a, d.H, vel, d.noise, st) != VC_OK)
+      return e->fail(VC_ERR_UNSUPPORTED, "vc_phase_marginal: no kernel for H = %d", d.H);
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return e->fail(VC_ERR_HIP, "vc_phase_marginal: %s", hipGetErrorString(err));
   return VC_OK;
   VC_GUARD_END(e)
 }

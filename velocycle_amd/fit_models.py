@@ -491,6 +491,38 @@ class _FitBase:
             c0 += nc_r
         return P.merge_pit_shards(parts)
 
+    def phase_marginal(self, num_samples=None, seed=None, draws=None, bins=128, phase_prior="model", return_per_draw=False):
+        """Phase-marginal scoring of the fitted model's cells (not in the reference; the Bayesian twin of `Phases.from_cycle_mle`): every
+        cell's phase posterior on a grid of `bins` phases and its evidence with the phase integrated out, over draws of the gene-level
+        and global sites, as a `velocycle_amd.predictive.PhaseMarginal`.  num_samples / seed / draws as `predictive_density` (the
+        guide's ϕxy draws are not used); phase_prior as `predictive.phase_marginal`, a tensor for THIS rank's cells.  Cells sharded over
+        ranks: every rank scores its cells, the records are gathered and merged (`predictive.merge_marginal_shards`)."""
+        from . import predictive as P
+        if self.engine is None or getattr(self, "losses", None) is None:
+            raise ValueError("phase_marginal: the model has not been fitted (call fit() first)")
+        sp = self.spec
+        n = int(self.num_samples if num_samples is None else num_samples) if draws is None else P._draw_count(draws, phixy=False)
+        P.check_marginal_request(sp.noisemodel, n, bins, self.engine.Nc_local, phase_prior)
+        eng = self.engine
+        if draws is None:
+            base = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if seed is None else int(seed)
+            base = broadcast_int(base, self._pg, eng.device)
+            names = [k for k in ("ν", "Δν", "shape_inv", "logγg", "logβg", "νω") if self._site_exists(k)]
+            draws = eng.sample_posterior(names, n, seed=base, step0=0)
+        rec = P.phase_marginal(eng, draws, bins=bins, phase_prior=phase_prior, return_per_draw=return_per_draw)
+        if self._world == 1:
+            return rec
+        dev = eng.device
+        ev = self._gather(rec.log_evidence.to(dev), 0)
+        post = self._gather(rec.posterior.to(dev), 0)
+        pd_ = self._gather(rec.per_draw.to(dev), 1) if rec.per_draw is not None else None
+        parts, c0 = [], 0
+        for nc_r in self._shard_sizes:
+            parts.append(P.PhaseMarginal(log_evidence=ev[c0:c0 + nc_r].clone(), posterior=post[c0:c0 + nc_r].clone(), phis=rec.phis,
+                                         n_draws=rec.n_draws, per_draw=None if pd_ is None else pd_[:, c0:c0 + nc_r].clone()))
+            c0 += nc_r
+        return P.merge_marginal_shards(parts)
+
     def _gather_ranks(self, local: torch.Tensor) -> torch.Tensor:
         """(world, *local.shape): every rank's copy of a replicated-shape tensor, in rank order."""
         return gather_cells(local.unsqueeze(0).to(self.engine.device), 0, [1] * self._world, self._pg)

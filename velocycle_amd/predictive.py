@@ -86,16 +86,18 @@ def check_request(noisemodel: str, n_draws: int, Ng: int, Nc: int, n_matrices: i
                          "use the per-gene / per-cell sums")
 
 
-def _draw_count(draws) -> int:
-    if "ν" not in draws or "ϕxy" not in draws:
-        raise ValueError("draws must hold at least the sites 'ν' and 'ϕxy' (what HipEngine.sample_posterior returns)")
+def _draw_count(draws, phixy: bool = True) -> int:
+    """phixy=False (phase_marginal): 'ϕxy' is neither required nor counted."""
+    if "ν" not in draws or (phixy and "ϕxy" not in draws):
+        raise ValueError("draws must hold at least the sites 'ν' and 'ϕxy' (what HipEngine.sample_posterior returns)" if phixy else
+                         "draws must hold at least the site 'ν'")
     # a site that is the same in every draw may be given once: the number of draws is the longest leading dimension
-    return max(int(draws[k].shape[0]) for k in ("ν", "ϕxy", "logγg", "logβg", "νω") if k in draws)
+    return max(int(draws[k].shape[0]) for k in ("ν", "ϕxy", "logγg", "logβg", "νω") if k in draws and (phixy or k != "ϕxy"))
 
 
-def _device_draws(engine, draws, D):
+def _device_draws(engine, draws, D, phixy: bool = True):
     """The sites of this engine's model out of `draws` as contiguous float32 device tensors: ({site: pointer}, {site: draw stride in
-    floats, 0 for a site that is the same in every draw}, the tensors to keep alive)."""
+    floats, 0 for a site that is the same in every draw}, the tensors to keep alive).  phixy=False: without 'ϕxy'."""
     sp = engine.spec
     vel = sp.kind == "velocity"
     Ng, Nc = sp.Ng, engine.Nc_local
@@ -108,6 +110,8 @@ def _device_draws(engine, draws, D):
         need["shape_inv"] = (Ng,)
     if vel:
         need.update({"logγg": (Ng,), "logβg": (Ng,), "νω": (sp.Nx, sp.Nhw)})
+    if not phixy:
+        del need["ϕxy"]
     fixed_sites = {"Δν", "shape_inv"}                     # Delta sites of both guides: one value
     ptr, stride, keep = {}, {}, []
     for name, shape in need.items():
@@ -500,3 +504,193 @@ def merge_pit_shards(parts) -> PredictivePIT:
     cell = {m: torch.cat([p.cell_hist[m] for p in parts], dim=0) for m in first.cell_hist}
     pw = None if first.pointwise is None else {m: torch.cat([p.pointwise[m] for p in parts], dim=2) for m in first.pointwise}
     return PredictivePIT(gene_hist=gene, cell_hist=cell, n_draws=first.n_draws, bins=first.bins, seed=first.seed, pointwise=pw)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# phase-marginal scoring: the phase posterior of every cell on a grid and its evidence with the phase integrated out
+# (vc_phase_marginal, csrc/vc_phase_marginal.hip)
+# ----------------------------------------------------------------------------------------------------------------------------------
+PM_MIN_BINS, PM_MAX_BINS = 2, 4096
+PHASE_PRIORS = ("model", "flat")
+_PN_ASYMPTOTIC = 12.0                # beyond this |t| the cancelling 1 - s R(s) of the projected normal is summed as a series
+
+
+def projected_normal_logpdf(m: torch.Tensor, phi: torch.Tensor) -> torch.Tensor:
+    """log density of the angle of x ~ Normal(m, I) in the plane (the projected normal), float64:
+    p(phi) = (1 / 2 pi) exp(-|m|^2 / 2) [1 + t Phi(t) / phi(t)],  t = m . (cos phi, sin phi).
+    m: (..., 2), phi broadcastable against m[..., 0].  t >= 0: log1p of exp(log t + log_ndtr(t) + t^2 / 2 + log sqrt(2 pi)); t < 0:
+    1 - s R(s), s = -t, R the Mills ratio, which cancels: directly up to s = 12 (error ~ s^4 eps), beyond by its asymptotic series
+    sum_n (-1)^(n+1) (2n - 1)!! / s^(2n)."""
+    m = torch.as_tensor(m, dtype=torch.float64)
+    phi = torch.as_tensor(phi, dtype=torch.float64)
+    t = m[..., 0] * torch.cos(phi) + m[..., 1] * torch.sin(phi)
+    half_log_2pi = 0.5 * math.log(2.0 * math.pi)
+    tp = t.clamp(min=1e-300)
+    pos = torch.nn.functional.softplus(torch.log(tp) + torch.special.log_ndtr(tp) + 0.5 * tp * tp + half_log_2pi, threshold=700.0)
+    s = (-t).clamp(min=0.0)
+    sm = s.clamp(max=_PN_ASYMPTOTIC)
+    direct = torch.log1p(-sm * torch.exp(torch.special.log_ndtr(-sm) + 0.5 * sm * sm + half_log_2pi))
+    sl = s.clamp(min=_PN_ASYMPTOTIC)
+    inv2 = 1.0 / (sl * sl)
+    term = inv2.clone()
+    series = term.clone()
+    for n in range(2, 21):
+        term = -term * (2 * n - 1) * inv2
+        series = series + term
+    neg = torch.where(s > _PN_ASYMPTOTIC, torch.log(series), direct)
+    bracket = torch.where(t > 0, pos, neg)
+    return -math.log(2.0 * math.pi) - 0.5 * (m * m).sum(-1) + bracket
+
+
+def phase_grid(bins: int) -> torch.Tensor:
+    """phi_j = 2 pi j / bins, float64 (the grid of the reference's from_cycle_mle, phases.py:495)."""
+    return 2.0 * math.pi * torch.arange(int(bins), dtype=torch.float64) / int(bins)
+
+
+def phase_log_prior(phixy_prior: torch.Tensor, bins: int) -> torch.Tensor:
+    """(Nc, bins) float64 log prior mass of every grid bin under the model's Normal(ϕxy_prior[c], I) on the direction
+    (velocity_inference_model.py:337): the projected-normal density at the grid phases, normalised to mass 1 on the grid."""
+    m = torch.as_tensor(phixy_prior, dtype=torch.float64).reshape(-1, 2)
+    lp = projected_normal_logpdf(m[:, None, :], phase_grid(bins)[None, :])
+    return lp - torch.logsumexp(lp, dim=1, keepdim=True)
+
+
+def projected_normal_resultant(kappa) -> torch.Tensor:
+    """Mean resultant length of the projected normal of Normal(m, I), |m| = kappa: sqrt(pi / 8) kappa e^(-z) (I0(z) + I1(z)), z = kappa^2 / 4."""
+    k = torch.as_tensor(kappa, dtype=torch.float64)
+    z = 0.25 * k * k
+    return math.sqrt(math.pi / 8.0) * k * (torch.special.i0e(z) + torch.special.i1e(z))
+
+
+def concentration_of_resultant(R, kappa_max: float = 1.0e3) -> torch.Tensor:
+    """The kappa in [0, kappa_max] whose projected normal has mean resultant length R (monotone: bisection in float64)."""
+    R = torch.as_tensor(R, dtype=torch.float64).clamp(0.0, 1.0)
+    lo, hi = torch.zeros_like(R), torch.full_like(R, float(kappa_max))
+    for _ in range(80):
+        mid = 0.5 * (lo + hi)
+        below = projected_normal_resultant(mid) < R
+        lo, hi = torch.where(below, mid, lo), torch.where(below, hi, mid)
+    return 0.5 * (lo + hi)
+
+
+@dataclass
+class PhaseMarginal:
+    """The phase of every cell integrated over a grid, CPU tensors.
+
+    log_evidence (Nc,) float64: log (1/D) sum_d sum_j exp a[d,c,j], the cell's log predictive density with the phase integrated out
+    posterior    (Nc, bins) float32: the phase posterior on the grid; rows sum to 1
+    phis         (bins,) float64: the grid 2 pi j / bins
+    per_draw     (D, Nc) float64 log sum_j exp a[d,c,j], when asked for."""
+    log_evidence: torch.Tensor
+    posterior: torch.Tensor
+    phis: torch.Tensor
+    n_draws: int
+    per_draw: Optional[torch.Tensor] = None
+
+    def _moments(self):
+        p = self.posterior.double()
+        return p @ torch.cos(self.phis), p @ torch.sin(self.phis)
+
+    @property
+    def mean_phase(self) -> torch.Tensor:
+        """Circular mean of the posterior in [0, 2 pi), (Nc,) float64."""
+        c, s = self._moments()
+        return torch.remainder(torch.atan2(s, c), 2.0 * math.pi)
+
+    @property
+    def resultant_length(self) -> torch.Tensor:
+        c, s = self._moments()
+        return torch.sqrt(c * c + s * s)
+
+    @property
+    def entropy(self) -> torch.Tensor:
+        """-sum_j post log post of every row (0 log 0 = 0); log(bins) for a flat row."""
+        p = self.posterior.double()
+        return -(torch.where(p > 0, p * torch.log(p.clamp(min=1e-300)), torch.zeros_like(p))).sum(1)
+
+    @property
+    def map_phase(self) -> torch.Tensor:
+        return self.phis[self.posterior.argmax(1)]
+
+    @property
+    def elpd(self) -> float:
+        return float(self.log_evidence.sum())
+
+
+def check_marginal_request(noisemodel: str, n_draws: int, bins: int, Nc: int, phase_prior):
+    """The refusals of phase_marginal that need no device: raised before any library or GPU call."""
+    _check_noisemodel("phase_marginal", noisemodel)
+    if int(n_draws) < 1:
+        raise ValueError(f"phase_marginal needs at least 1 draw, got {n_draws}")
+    if int(bins) != bins or not PM_MIN_BINS <= int(bins) <= PM_MAX_BINS:
+        raise ValueError(f"phase_marginal: bins must be an integer in [{PM_MIN_BINS}, {PM_MAX_BINS}], got {bins}")
+    if isinstance(phase_prior, str):
+        if phase_prior not in PHASE_PRIORS:
+            raise ValueError(f"phase_marginal: phase_prior must be one of {PHASE_PRIORS} or a (cells, bins) tensor of log masses, got {phase_prior!r}")
+    elif tuple(torch.as_tensor(phase_prior).shape) != (int(Nc), int(bins)):
+        raise ValueError(f"phase_marginal: the prior tensor has shape {tuple(torch.as_tensor(phase_prior).shape)}, expected ({Nc}, {bins})")
+
+
+def phase_marginal(engine, draws: Dict[str, torch.Tensor], *, bins: int = 128, phase_prior="model", return_per_draw: bool = False,
+                   chunk_cells: Optional[int] = None) -> PhaseMarginal:
+    """The phase posterior on a grid of `bins` phases and the evidence with the phase integrated out, of every cell this engine holds,
+    under explicit draws of the gene-level and global sites (as `pointwise_density` takes them; "ϕxy" is ignored and not required).
+    The engine's cells need not be cells a fit has seen: a held-out cell's predictive density is this evidence.
+    phase_prior: "flat" (log mass -log bins), "model" (the angle density of the model's Normal(ϕxy_prior[c], I), `phase_log_prior`,
+    formed on the host in float64) or a (cells, bins) tensor of log masses, used as given (the device reads float32).
+    chunk_cells: cells per library call (default: all); the result does not depend on it.  For the velocity model the integrand is not
+    smooth in the phase: the evidence is that of the discrete grid.  There is no CPU path."""
+    sp = engine.spec
+    D = _draw_count(draws, phixy=False)
+    Ng, Nc = sp.Ng, engine.Nc_local
+    check_marginal_request(sp.noisemodel, D, bins, Nc, phase_prior)
+    _check_fast_set("phase_marginal", engine)
+    B = int(bins)
+    dev = engine.device
+    if isinstance(phase_prior, str):
+        lw = None if phase_prior == "flat" else phase_log_prior(torch.as_tensor(sp.phixy_prior)[engine.c0:engine.c1], B)
+    else:
+        lw = torch.as_tensor(phase_prior)
+    if lw is not None:
+        lw = lw.to(device=dev, dtype=torch.float32).contiguous()
+    ptr, stride, keep = _device_draws(engine, draws, D, phixy=False)
+    evidence = torch.empty((Nc,), dtype=torch.float64, device=dev)
+    post = torch.empty((Nc, B), dtype=torch.float32, device=dev)
+    per_draw = torch.empty((D, Nc), dtype=torch.float64, device=dev) if return_per_draw else None
+    step = Nc if not chunk_cells else max(1, int(chunk_cells))
+    g = lambda k: ptr.get(k)
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    for c0 in range(0, Nc, step):
+        engine._check(engine.lib.vc_phase_marginal(
+            engine._h, C.c_int64(D), g("ν"), C.c_int64(stride["ν"]), g("Δν"), g("shape_inv"), g("logγg"), C.c_int64(stride.get("logγg", 0)),
+            g("logβg"), C.c_int64(stride.get("logβg", 0)), g("νω"), C.c_int64(stride.get("νω", 0)), C.c_int32(B), vp(lw), C.c_int64(c0),
+            C.c_int64(min(step, Nc - c0)), vp(evidence), vp(post), vp(per_draw), engine._stream()))
+    torch.cuda.synchronize(dev)
+    del keep
+    return PhaseMarginal(log_evidence=evidence.cpu(), posterior=post.cpu(), phis=phase_grid(B), n_draws=D,
+                         per_draw=None if per_draw is None else per_draw.cpu())
+
+
+def merge_marginal_shards(parts) -> PhaseMarginal:
+    """The records of the ranks of a cell-sharded evaluation, in rank order, as one record: every table concatenated over the cells."""
+    parts = list(parts)
+    first = parts[0]
+    if any(p.n_draws != first.n_draws or p.posterior.shape[1] != first.posterior.shape[1] for p in parts):
+        raise ValueError("merge_marginal_shards: the records come from different draws or grids")
+    if any((p.per_draw is None) != (first.per_draw is None) for p in parts):
+        raise ValueError("merge_marginal_shards: only some of the records hold per-draw values")
+    return PhaseMarginal(log_evidence=torch.cat([p.log_evidence for p in parts]), posterior=torch.cat([p.posterior for p in parts], dim=0),
+                         phis=first.phis, n_draws=first.n_draws,
+                         per_draw=None if first.per_draw is None else torch.cat([p.per_draw for p in parts], dim=1))
+
+
+def compare_evidence(a: PhaseMarginal, b: PhaseMarginal):
+    """Paired difference of two scorings of the same cells: (sum_c (a - b) of log_evidence, standard error sqrt(Nc var_c(diff_c)));
+    positive: the cells support `a`.  Like `compare`."""
+    if a.log_evidence.shape != b.log_evidence.shape:
+        raise ValueError(f"compare_evidence: the records hold {a.log_evidence.numel()} and {b.log_evidence.numel()} cells; only scorings "
+                         "of the same cells can be compared")
+    diff = (a.log_evidence - b.log_evidence).double()
+    n = diff.numel()
+    se = math.sqrt(n * float(diff.var(unbiased=True))) if n > 1 else float("nan")
+    return float(diff.sum()), se
