@@ -85,17 +85,24 @@ def assert_step_matches_oracle(eng, spec, eps, loss_rtol=1e-5, grad_rtol=2e-3):
     of the float64 oracle, every gradient block within `grad_rtol` of its max-norm -- or no worse than 4x the error of
     the oracle's own float32 run (= what the reference computes in) where the 1/(z + 1e-5) relu kink amplifies rounding."""
     torch.cuda.synchronize()
+    return assert_grads_match_oracle(eng.loss(), eng.named(eng.grad), eng.named(), spec, eps, loss_rtol, grad_rtol)
+
+
+def assert_grads_match_oracle(loss, grads, params, spec, eps, loss_rtol=1e-5, grad_rtol=2e-3):
+    """assert_step_matches_oracle's bars on a loss, named gradient blocks and the named parameters they were evaluated at, wherever
+    they come from (a fused step's gradient buffer and the parameters recorded in front of it, the ranks of a sharded step)."""
     p64 = problem_from_spec(spec, torch.float64)
-    par = {n: v.detach().cpu().double() for n, v in eng.named().items()}
+    par = {n: v.detach().cpu().double() for n, v in params.items()}
     e64 = {k: v.double() for k, v in eps.items() if not k.startswith("_")}
     l64, g64, _, _ = orc.loss_and_grads(p64, par, e64)
     _, g32, _, _ = orc.loss_and_grads(p64.to(torch.float32), {k: v.float() for k, v in par.items()},
                                       {k: v.float() for k, v in e64.items()})
-    assert abs(eng.loss() - l64) <= loss_rtol * abs(l64), (eng.loss(), l64)
-    for name, got in eng.named(eng.grad).items():
+    assert abs(loss - l64) <= loss_rtol * abs(l64), (loss, l64)
+    assert set(grads) == set(params), (sorted(grads), sorted(params))
+    for name, got in grads.items():
         want = g64[name].numpy()
         fin = np.isfinite(want)
-        err = np.abs(got.cpu().numpy()[fin] - want[fin]).max()
+        err = np.abs(got.detach().cpu().numpy()[fin] - want[fin]).max()
         ref32 = np.abs(g32[name].numpy().astype(np.float64)[fin] - want[fin]).max()
         strict = grad_rtol * max(np.abs(want[fin]).max(), 1e-3)
         assert err <= max(strict, 4 * ref32), (name, err, ref32)
@@ -107,6 +114,66 @@ def assert_step_matches_oracle(eng, spec, eps, loss_rtol=1e-5, grad_rtol=2e-3):
             print(f"[assert_step_matches_oracle] block {name!r} passed through the 4 x float32-oracle clause only: err {err:.3e} "
                   f"(strict bar {strict:.3e}), float32 oracle's own error {ref32:.3e}")
     return l64, g64
+
+
+DNU_ROW_RTOL, DNU_ROW_FLOOR = 2e-3, 1e-3
+
+
+def assert_dnu_rows_match_oracle(got, want64, label):
+    """The gradient of the per-batch offsets, `Δν_locs` (Nb, Ng), against the float64 oracle ROW BY ROW: for every batch q
+    max |got[q] - want[q]| <= 2e-3 x max(max |want[q]|, 1e-3) -- the gradient tolerance of DESIGN section 4 and the floor of
+    assert_step_matches_oracle, taken per batch instead of per block, and without its float32-oracle clause (Δν enters the constant
+    harmonic only: no path through the relu kink of ElogU; the float32 oracle's own row error is ~2e-4 of this bar,
+    tests/test_batch_rows_cpu.py).  An empty batch's row is exactly zero in the oracle and falls under the floor.
+
+    The CALLER asserts that the Δν values the gradient was evaluated at are exactly 0: there the Normal(0, sd) prior's term of the
+    gradient vanishes and row q is the likelihood sum over the workgroups (cells) of batch q alone -- a cell dropped, doubled or
+    accounted to a neighbouring batch moves the row by a cell's share, which a prior term of ~Δν / sd^2 (sd = 0.01 in the velocity
+    model: 500 per element at Δν = 0.05) otherwise buries under the block's max-norm.
+
+    Returns the worst err / bar of every row (numpy, (Nb,)) for the caller to print."""
+    got = np.asarray(got.detach().cpu().numpy() if torch.is_tensor(got) else got, dtype=np.float64)
+    want = np.asarray(want64.detach().cpu().numpy() if torch.is_tensor(want64) else want64, dtype=np.float64)
+    assert got.shape == want.shape and got.ndim == 2, (label, got.shape, want.shape)
+    assert np.isfinite(got).all() and np.isfinite(want).all(), label
+    err = np.abs(got - want).max(axis=1)
+    bar = DNU_ROW_RTOL * np.maximum(np.abs(want).max(axis=1), DNU_ROW_FLOOR)
+    ratio = err / bar
+    bad = np.nonzero(ratio > 1.0)[0]
+    assert bad.size == 0, (label, [(int(q), float(err[q]), float(bar[q])) for q in bad])
+    return ratio
+
+
+PLANTED_SIZES = (400, 264, 0, 3)       # batch 0, batch 7, the empty batch, the tiny batch of onehot_layout's planted layouts
+
+
+def onehot_layout(Nc, name, Nb, ids=None):
+    """A batch id per cell (int64, (Nc,)) of the layouts the per-batch tests run:
+      "interleaved": `ids` as they are (the random ids tests.test_hip_sweep._problem drew; without `ids`: drawn here from a generator
+                     seeded by (Nc, Nb)) -- the engine reorders the cells by batch;
+      "contiguous":  the same ids stably sorted (anndata.concat(..., label="batch"));
+      "planted":     contiguous batches of planted sizes, Nb = 9 or 8: batch 0 has 400 cells and batch 7 has 264 (at 8 cells per
+                     chunk, Tuning(cells_per_wave=2), 50 and 33 chunks: past the 32 rows the range sums request per trip), batch 2
+                     is EMPTY, batch 4 has 3 cells (fewer than the 4 waves of a workgroup), the other batches share the rest evenly."""
+    if name in ("interleaved", "contiguous"):
+        if ids is None:
+            ids = torch.randint(0, Nb, (Nc,), generator=torch.Generator().manual_seed(1000 * Nb + Nc))
+        ids = torch.as_tensor(ids).long().reshape(-1)
+        assert ids.numel() == Nc and int(ids.min()) >= 0 and int(ids.max()) < Nb
+        return ids if name == "interleaved" else ids[torch.argsort(ids, stable=True)]
+    if name != "planted" or Nb not in (8, 9):
+        raise ValueError((name, Nb))
+    sizes = {0: PLANTED_SIZES[0], 7: PLANTED_SIZES[1], 2: PLANTED_SIZES[2], 4: PLANTED_SIZES[3]}
+    rest = [q for q in range(Nb) if q not in sizes]
+    left = Nc - sum(sizes.values())
+    assert left >= len(rest), (Nc, Nb)
+    for i, q in enumerate(rest):
+        sizes[q] = left // len(rest) + (1 if i < left % len(rest) else 0)
+    return torch.cat([torch.full((sizes[q],), q, dtype=torch.long) for q in range(Nb)])
+
+
+def onehot_Db(ids, Nb, dtype=torch.float64):
+    return torch.stack([(ids == q).to(dtype) for q in range(Nb)])
 
 
 # how often assert_step_matches_oracle's second clause (<= 4 x the float32 oracle's own error) was what let a gradient block pass;

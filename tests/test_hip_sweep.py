@@ -71,6 +71,21 @@ def _check(p, gpl=None, tuning=None):
         fin = np.isfinite(want)
         err = np.abs(got.cpu().numpy()[fin] - want[fin]).max() if fin.any() else 0.0
         assert err <= 3e-3 * max(np.abs(want[fin]).max() if fin.any() else 0, 1e-2), (name, err)
+    onehot_db = bool(((p.Db == 0) | (p.Db == 1)).all() and (p.Db.sum(0) == 1).all())
+    if p.with_delta_nu and onehot_db and "Δν_locs" in par:
+        # learned one-hot batch offsets: the same perturbed parameters and draws with Δν_locs = 0, where the prior term of its
+        # gradient vanishes and row q is the likelihood sum over batch q's cells -- held per ROW (helpers.assert_dnu_rows_match_oracle;
+        # the block-wise bar above is set by the prior term, ~500 per element in the velocity model, and cannot see a batch)
+        from tests.helpers import assert_dnu_rows_match_oracle
+        par0 = dict(par, **{"Δν_locs": torch.zeros_like(par["Δν_locs"])})
+        eng.set_params({k: v.float() for k, v in par0.items()})
+        assert not bool(eng.named()["Δν_locs"].any())
+        eng.elbo_grad(eps=eng.pack_eps({k: v.float() for k, v in eps.items() if not k.startswith("_")}))
+        torch.cuda.synchronize()
+        _, g0, _, _ = orc.loss_and_grads(p, {k: v.float().double() for k, v in par0.items()}, eps32)
+        ratio = assert_dnu_rows_match_oracle(eng.named(eng.grad)["Δν_locs"], g0["Δν_locs"],
+                                             f"{eng.stats['main_kernel']} Nb={p.Nb} Nc={p.Nc} Ng={p.Ng}")
+        print(f"[dnu rows, parity mode] Nb={p.Nb} Nc={p.Nc}: worst err / bar {ratio.max():.2e}")
     kind = eng.stats["main_kernel"]
     # batch offsets: a one-hot design matrix is folded per workgroup (the kernel's NB is 0 for any number of batches) unless the
     # tuning asks for the dense contraction; anything else keeps NB = Nb (or the run-time-sized set beyond 4 batches)
