@@ -176,6 +176,142 @@ def onehot_Db(ids, Nb, dtype=torch.float64):
     return torch.stack([(ids == q).to(dtype) for q in range(Nb)])
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The angular-speed coefficients: d loglik / d nu_omega[x, h] = sum_c A3_c D[x, c] zeta_omega_h(phi_c), one row per CONDITION x.
+# ---------------------------------------------------------------------------------------------------------------------
+NUW_ROW_RTOL, NUW_ROW_FLOOR, NUW_REST_RTOL = 2e-3, 1e-3, 1e-6
+# |sin k phi, cos k phi of the kernels (float32: vc_dir_sincos + the harmonics' recurrence) - the float64 oracle's| <= k x this;
+# see assert_omega_matches_oracle
+OMEGA_SINCOS_ERR = 4e-7
+
+
+def condition_layout(ids, Nb, Nx, name):
+    """A (Nx, Nc) one-hot condition design D (float64) from a batch id per cell (onehot_layout; "planted": batch 4 has three cells,
+    batch 2 none).  The TINY batch is the smallest batch that has cells, the tiny condition is the LAST one, Nx - 1:
+      "tiny_last":  the tiny batch is alone in the last condition (the empty batches are nominally there too: no cell says so);
+                    batch q of the others is in condition q mod (Nx - 1) -- constant within every batch;
+      "empty_cond": the same with condition 1 left without any cell (Nx >= 3): the others are dealt out over 0, 2, .., Nx - 2;
+      "scattered":  NOT constant within the batches (`ids` only gives Nc): the tiny condition's three cells are cell 0, cell Nc // 2
+                    and cell Nc - 1, every other cell c is in condition c mod (Nx - 1)."""
+    ids = torch.as_tensor(ids).long().reshape(-1)
+    Nc = ids.numel()
+    assert Nx >= 2 and Nc >= 4, (Nx, Nc)
+    if name == "scattered":
+        cond = torch.arange(Nc) % (Nx - 1)
+        cond[[0, Nc // 2, Nc - 1]] = Nx - 1
+    elif name in ("tiny_last", "empty_cond"):
+        n = torch.bincount(ids, minlength=Nb)
+        assert n.numel() == Nb
+        tiny = int(torch.where(n > 0, n, n.max() + 1).argmin())
+        slots = list(range(Nx - 1))
+        if name == "empty_cond":
+            if Nx < 3:
+                raise ValueError("an empty condition beside the tiny one needs Nx >= 3")
+            slots.remove(1)
+        of_batch = torch.tensor([Nx - 1 if (q == tiny or int(n[q]) == 0) else slots[q % len(slots)] for q in range(Nb)])
+        cond = of_batch[ids]
+    else:
+        raise ValueError(name)
+    return torch.stack([(cond == x).double() for x in range(Nx)])
+
+
+def nuw_row_blocks(grads, spec):
+    """{name: float64 array (Nx, Nhw * k)} of every parameter block with one row per (condition, coefficient): mean-field `νω_locs`,
+    `νω_scales` (k = 1); LRMN the last Nx Nhw entries of `loc` and `cov_diag` (k = 1) and the last Nx Nhw rows of `cov_factor`
+    (k = R).  Non-finite entries (log-parameters at -inf: cov_factor zeros) are NaN in the result: the callers keep them out of every
+    maximum, as assert_grads_match_oracle does."""
+    Nx, Nhw = spec.Nx, spec.Nhw
+    n = Nx * Nhw
+    out = {}
+
+    def put(name, t, key=None):
+        a = np.array(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.float64)
+        a = a.reshape(-1, a.shape[-1])[-n:] if name == "cov_factor" else a.reshape(-1)[-n:]
+        a = a.reshape(Nx, -1)
+        a[~np.isfinite(a)] = np.nan
+        out[key or name] = a
+
+    if spec.guide == "meanfield":
+        put("νω_locs", grads["νω_locs"])
+        put("νω_scales", grads["νω_scales"])
+    else:
+        put("loc", grads["loc"], "loc[νω]")
+        put("cov_diag", grads["cov_diag"], "cov_diag[νω]")
+        put("cov_factor", grads["cov_factor"], "cov_factor[νω]")
+    return out
+
+
+def _rowmax(a):
+    """max |a| of every row, NaN (kept out) entries aside; 0 for a row of nothing else."""
+    return np.nan_to_num(np.abs(a), nan=0.0).max(axis=1)
+
+
+def nuw_row_bars(params, spec, eps):
+    """(want, lik, rest, bar): the float64 oracle's nuw_row_blocks at `params` / `eps`; `rest` = the same call with D = 0 -- then
+    omega == 0, no nu_omega-related parameter has a path to the likelihood, and what is left of those rows is exactly their prior +
+    entropy part; lik = want - rest; bar[name] (Nx,) = 2e-3 x max(max |lik[x]|, 1e-3) + 1e-6 x max |rest[x]| -- the gradient tolerance
+    of DESIGN section 4 per CONDITION on the likelihood sum alone, plus 8 float32 roundings of the prior / entropy part (all there is
+    in the row of a condition without cells)."""
+    p64 = problem_from_spec(spec, torch.float64)
+    par = {n: v.detach().cpu().double() for n, v in params.items()}
+    e64 = {k: v.detach().cpu().double() for k, v in eps.items() if not k.startswith("_")}
+    _, g, _, _ = orc.loss_and_grads(p64, par, e64)
+    p0 = orc.Problem(**{**p64.__dict__, "D": torch.zeros_like(p64.D)})
+    _, g0, _, _ = orc.loss_and_grads(p0, par, e64)
+    want, rest = nuw_row_blocks(g, spec), nuw_row_blocks(g0, spec)
+    lik = {k: want[k] - rest[k] for k in want}
+    bar = {k: NUW_ROW_RTOL * np.maximum(_rowmax(lik[k]), NUW_ROW_FLOOR) + NUW_REST_RTOL * _rowmax(rest[k]) for k in want}
+    return want, lik, rest, bar
+
+
+def assert_nuw_rows_match_oracle(grads, params, spec, eps, label):
+    """Every nu_omega-related gradient row against the float64 oracle PER CONDITION (nuw_row_bars): for every block of nuw_row_blocks
+    and every condition x, max |got[x] - want[x]| <= bar[x].  No float32-oracle clause: tests/test_nuw_rows_cpu.py holds the float32
+    oracle's own rows to <= 0.25 of this bar on every case the GPU tests run.  A block-wide bar cannot see a small condition: a row
+    of three cells is 100-900 times smaller than the block's max-norm, a cell of a neighbouring batch added to it passes, and so does
+    the row stored as zero.  Returns {block: err / bar per condition (Nx,)} for the caller to print."""
+    want, _, _, bar = nuw_row_bars(params, spec, eps)
+    got = nuw_row_blocks(grads, spec)
+    assert set(got) == set(want), (label, sorted(got), sorted(want))
+    out, bad = {}, []
+    for k in want:
+        assert got[k].shape == want[k].shape and np.array_equal(np.isnan(got[k]), np.isnan(want[k])), (label, k)
+        err = _rowmax(got[k] - want[k])
+        out[k] = err / bar[k]
+        bad += [(k, int(x), float(err[x]), float(bar[k][x])) for x in np.nonzero(out[k] > 1.0)[0]]
+    assert not bad, (label, bad)
+    return out
+
+
+def assert_omega_matches_oracle(omega, params, spec, eps, label):
+    """The forward side: the angular speed of every cell (read_site("ω") behind a sample at `params` with the draws `eps`) against
+    the float64 oracle's det["ω"] = sum_x D[x, c] sum_h nu_omega[x, h] zeta_omega_h(phi_c).  Bar per cell:
+        16 eps32 x sum_x D[x, c] sum_h |nu_omega[x, h] zeta_omega_h(phi_c)|          (the sample, the products, the sum)
+      + OMEGA_SINCOS_ERR x sum_x D[x, c] sum_k k (|nu_omega[x, 2k - 1]| + |nu_omega[x, 2k]|)   (sin k phi, cos k phi in float32).
+    OMEGA_SINCOS_ERR = 4e-7 = 4 x the 9.6e-8 measured once on an MI355X against the float64 oracle, on the mean-field joint cases of
+    tests/test_nuw_rows_cpu.py (800, 2 100 and 3 200 cells, Hw = 1 and 3) with the constant coefficient set to 0 and every harmonic
+    coefficient to 1, so that omega_c = sum_k sin k phi_c + cos k phi_c: max_c |omega_c - float64| / sum_k 2 k = 6.0e-8 .. 9.6e-8 per
+    case (median 1.5e-8) -- the rounding of that sum included.  On the cases as they are the whole error was at most 2.9 eps32 of the
+    first term's scale (the K_pre sample; 2.6 for the chain's), so the first term's 16 leaves 5 x.
+    With the cases' coefficients 0.2 apart between conditions, a cell evaluated with another condition's row is ~1e5 bars off.
+    Returns the worst err / bar."""
+    p64 = problem_from_spec(spec, torch.float64)
+    par = {n: v.detach().cpu().double() for n, v in params.items()}
+    e64 = {k: v.detach().cpu().double() for k, v in eps.items() if not k.startswith("_")}
+    _, val, det = orc.elbo_loss(p64, par, e64)
+    nuw, zw, D = val["νω"].detach().numpy(), det["ζω"].detach().numpy(), p64.D.numpy()        # (Nx, Nhw), (Nhw, Nc), (Nx, Nc)
+    want = det["ω"].detach().numpy()
+    k = (np.arange(spec.Nhw) + 1) // 2
+    scale = np.einsum("xc,xh,hc->c", np.abs(D), np.abs(nuw), np.abs(zw))
+    bar = 16 * float(np.finfo(np.float32).eps) * scale + OMEGA_SINCOS_ERR * (np.abs(D).T @ (np.abs(nuw) @ k))
+    got = np.asarray(omega.detach().cpu().numpy() if torch.is_tensor(omega) else omega, dtype=np.float64).reshape(-1)
+    assert got.shape == want.shape and np.isfinite(got).all(), (label, got.shape, want.shape)
+    ratio = np.abs(got - want) / np.maximum(bar, 1e-300)
+    bad = np.nonzero(ratio > 1.0)[0]
+    assert bad.size == 0, (label, [(int(c), float(got[c]), float(want[c]), float(bar[c])) for c in bad[:8]], int(bad.size))
+    return float(ratio.max())
+
+
 # how often assert_step_matches_oracle's second clause (<= 4 x the float32 oracle's own error) was what let a gradient block pass;
 # tests/conftest.py prints the tally at the end of a run
 CLAUSE_STATS = {"blocks": 0, "by_ref32_clause": []}
