@@ -1,5 +1,6 @@
 """Shared test helpers: fixtures -> oracle Problem / product ModelSpec."""
 import glob
+import math
 import os
 
 import numpy as np
@@ -97,7 +98,8 @@ def assert_grads_match_oracle(loss, grads, params, spec, eps, loss_rtol=1e-5, gr
     l64, g64, _, _ = orc.loss_and_grads(p64, par, e64)
     _, g32, _, _ = orc.loss_and_grads(p64.to(torch.float32), {k: v.float() for k, v in par.items()},
                                       {k: v.float() for k, v in e64.items()})
-    assert abs(loss - l64) <= loss_rtol * abs(l64), (loss, l64)
+    if loss is not None:          # (None: a step of the gradient-only kernels, whose loss is not formed -- the caller asserts the NaN)
+        assert abs(loss - l64) <= loss_rtol * abs(l64), (loss, l64)
     assert set(grads) == set(params), (sorted(grads), sorted(params))
     for name, got in grads.items():
         want = g64[name].numpy()
@@ -310,6 +312,151 @@ def assert_omega_matches_oracle(omega, params, spec, eps, label):
     bad = np.nonzero(ratio > 1.0)[0]
     assert bad.size == 0, (label, [(int(c), float(got[c]), float(want[c]), float(bar[c])) for c in bad[:8]], int(bad.size))
     return float(ratio.max())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The likelihood kernel's cell loop: every gene-level gradient is a sum over ALL cells, and in the U-only kernels a cell reaches nothing
+# else.  Lit-cell probe data make one cell a large share of one gene's row; the rows are then held to the oracle per GENE.
+# ---------------------------------------------------------------------------------------------------------------------
+LIT_COUNT = 200.0          # the lit entries: an integer < 2048 (uint16 storage and the dense histogram tables stay selectable)
+LIT_LEVEL = -4.0           # mu_nu[:, 0] of the count models: an unlit entry's mean term is ~1e-2 of a lit entry's
+LIT_Z_MIN = 0.3            # z = omega nu.zeta' + gamma of every (gene, cell): nowhere near the relu kink of ElogU
+GENE_ROW_RTOL, GENE_ROW_FLOOR = DNU_ROW_RTOL, DNU_ROW_FLOOR
+
+
+def lit_cell_problem(p, amp=None, seed=0):
+    """A problem of tests.test_hip_sweep._problem (float64 oracle Problem) turned into a lit-cell probe; returns a new Problem.
+      counts:  zero except S[c mod Ng, c] = U[(c + 1) mod Ng, c] = LIT_COUNT: every cell lit in exactly one gene per matrix, every
+               gene in m ~ Nc / Ng cells;
+      level:   mu_nu[:, 0] = LIT_LEVEL + 0.1 x noise; a conditioned nu follows.  Lognormal noise: the data are log(k + 1) and an unlit
+               entry's residual is its own log-mean / sigma^2, so the means are put where the unlit entries ARE -- mu_nu[:, 0],
+               mu_beta and mu_gamma 0 + 0.005 x noise, sd_nu[:, 0] 0.02, sd_beta 0.01: a gene's ~1 000 unlit residuals then stay
+               under its m lit ones;
+      phases:  cell c sits at phi_c = c (pi + 0.37) + 0.1 x noise (prior and conditioned value), the first harmonic of gene g at the
+               angle g pi / 2 + 0.1 x noise: neighbouring cells lie opposite each other, neighbouring genes a quarter turn apart, so
+               of the two genes lit in a pair of neighbouring cells at least one sees |cos| differ by ~1.4 between the two (random
+               phases leave pairs whose gamma / z coincide: an exchange there moved no row by more than 2.1 bars);
+      kink:    the harmonics' amplitudes a_k (all of `amp` = 0.65 for H = 1; else `amp` = 0.5, 0.8 amp for k = 1 and the rest shared
+               as 1 / k at random angles) have sum_k k a_k = amp, so |nu.zeta'| <= amp; gamma = exp(0.05 x noise),
+               nu_omega's constant as `p` has it (0.4 + 0.05 x noise), prior sds of the harmonics of nu, of log gamma and of nu_omega
+               0.01 / 0.05 / 0.02 so that a draw stays where the mean is.  Asserted here, in float64 at the prior means:
+               z = omega nu.zeta' + gamma >= LIT_Z_MIN + 0.15 for every (gene, cell); assert_gene_rows_match_oracle asserts
+               z >= LIT_Z_MIN at the point a gradient was evaluated at.
+    gamma / z then ranges over ~[0.75, 1.6] from cell to cell: a cell evaluated with its neighbour's record shows in d / d log gamma."""
+    g = torch.Generator().manual_seed(977 + seed)
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    Ng, Nc, Hh = p.Ng, p.Nc, p.H
+    cells = torch.arange(Nc)
+    S = torch.zeros(Ng, Nc, dtype=torch.float64)
+    S[cells % Ng, cells] = LIT_COUNT
+    kw = dict(p.__dict__)
+    kw["S"] = S
+    lognormal = p.noisemodel == "Lognormal"
+    mu_nu, sd_nu = p.mu_nu.clone(), p.sd_nu.clone()
+    amp = amp if amp is not None else (0.65 if Hh == 1 else 0.5)
+    mu_nu[:, 0] = 0.005 * r(Ng) if lognormal else LIT_LEVEL + 0.1 * r(Ng)
+    first = 1.0 if Hh == 1 else 0.8
+    for k in range(1, Hh + 1):
+        a_k = amp * first if k == 1 else amp * (1.0 - first) / ((Hh - 1) * k)
+        ang = (0.5 * math.pi * torch.arange(Ng, dtype=torch.float64) + 0.1 * r(Ng)) if k == 1 else \
+            2 * math.pi * torch.rand(Ng, generator=g, dtype=torch.float64)
+        mu_nu[:, 2 * k - 1], mu_nu[:, 2 * k] = a_k * torch.cos(ang), a_k * torch.sin(ang)
+    sd_nu[:, 1:] = 0.01
+    if lognormal:
+        sd_nu[:, 0] = 0.02
+    kw["mu_nu"], kw["sd_nu"] = mu_nu, sd_nu
+    phi = (math.pi + 0.37) * cells.double() + 0.1 * r(Nc)
+    kw["phixy_prior"] = 2.0 * torch.stack([torch.cos(phi), torch.sin(phi)], 1)
+    cond = {k: v.clone() for k, v in p.condition_on.items()}
+    if "ϕxy" in cond:
+        cond["ϕxy"] = kw["phixy_prior"] + 0.02 * r(Nc, 2)
+    if "ν" in cond:
+        cond["ν"] = mu_nu + torch.cat([(0.005 if lognormal else 0.05) * r(Ng, 1), 0.01 * r(Ng, 2 * Hh)], 1)
+    if p.kind == "velocity":
+        U = torch.zeros(Ng, Nc, dtype=torch.float64)
+        U[(cells + 1) % Ng, cells] = LIT_COUNT
+        kw["U"] = U
+        kw["mu_gamma"], kw["sd_gamma"] = (0.005 if lognormal else 0.05) * r(Ng), torch.full((Ng,), 0.05, dtype=torch.float64)
+        kw["sd_nuw"] = torch.full_like(p.sd_nuw, 0.02)
+        if lognormal:
+            kw["mu_beta"], kw["sd_beta"] = 0.005 * r(Ng), torch.full((Ng,), 0.01, dtype=torch.float64)
+        if "logγg" in cond:
+            cond["logγg"] = kw["mu_gamma"] + 0.02 * r(Ng)
+        if "logβg" in cond and lognormal:
+            cond["logβg"] = kw["mu_beta"] + 0.02 * r(Ng)
+    kw["condition_on"] = cond
+    q = type(p)(**kw)
+    if q.kind == "velocity":
+        par = orc.init_params(q, torch.zeros(q.Ng + q.Nx * q.Nhw, q.rho_rank, dtype=torch.float64))
+        zero = {k: torch.zeros_like(v) for k, v in orc.draw_eps(q, torch.Generator().manual_seed(0)).items()}
+        zmin = lit_z_min(q, par, zero)
+        assert zmin >= LIT_Z_MIN + 0.15, zmin
+    return q
+
+
+def lit_z_min(p, par, eps):
+    """min over (gene, cell) of z = omega nu.zeta'(phi) + gamma at the parameters `par` and draws `eps`, float64 (velocity models)."""
+    p64 = p if isinstance(p, orc.Problem) else problem_from_spec(p, torch.float64)
+    par = {n: v.detach().cpu().double() for n, v in par.items()}
+    e64 = {k: v.detach().cpu().double() for k, v in eps.items() if not k.startswith("_")}
+    _, val, det = orc.elbo_loss(p64, par, e64)
+    z = torch.einsum("gh,ch->gc", val["ν"], det["ζ_dϕ"]) * det["ω"] + det["γg"][:, None]
+    return float(z.min())
+
+
+def gene_row_blocks(grads, spec):
+    """{name: float64 array (rows, k)} of every parameter block with one row per GENE -- mean-field `ν_locs`, `ν_scales` (k = Nh),
+    `logγg_*`, `logβg_*`, `shape_inv_locs` (k = 1); LRMN the first Ng entries of `loc` and `cov_diag`, the first Ng rows of
+    `cov_factor` (k = R) and `rho_real_loc` -- and, where phi_xy is learned, `ϕxy_locs` with one row per CELL (k = 2).  Non-finite
+    entries are NaN in the result and kept out of every maximum (nuw_row_blocks)."""
+    Ng = spec.Ng
+    out = {}
+
+    def put(key, t, rows):
+        a = np.array(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.float64)
+        a = a.reshape(a.shape[0], -1)[:rows].copy()
+        a[~np.isfinite(a)] = np.nan
+        out[key] = a
+
+    for name in ("ν_locs", "ν_scales", "logγg_locs", "logγg_scales", "logβg_locs", "logβg_scales", "shape_inv_locs", "rho_real_loc"):
+        if name in grads:
+            put(name, grads[name], Ng)
+    for name in ("loc", "cov_diag", "cov_factor"):
+        if name in grads:
+            put(name + "[γ]", grads[name], Ng)
+    if "ϕxy" not in spec.condition_on and "ϕxy_locs" in grads:
+        put("ϕxy_locs", grads["ϕxy_locs"], spec.Nc)
+    return out
+
+
+def gene_row_ratios(got, want):
+    """{block: err / bar per row}: |got[g] - want[g]|_max / (GENE_ROW_RTOL x max(|want[g]|_max, GENE_ROW_FLOOR)) of gene_row_blocks."""
+    assert set(got) == set(want), (sorted(got), sorted(want))
+    out = {}
+    for k in want:
+        assert got[k].shape == want[k].shape and np.array_equal(np.isnan(got[k]), np.isnan(want[k])), k
+        out[k] = _rowmax(got[k] - want[k]) / (GENE_ROW_RTOL * np.maximum(_rowmax(want[k]), GENE_ROW_FLOOR))
+    return out
+
+
+def assert_gene_rows_match_oracle(grads, params, spec, eps, label):
+    """Every gene-indexed gradient block against the float64 oracle (on the float32-rounded parameters and draws) ROW BY ROW: for
+    every block of gene_row_blocks and every gene g, max |got[g] - want[g]| <= 2e-3 x max(max |want[g]|, 1e-3) -- DNU_ROW_RTOL /
+    DNU_ROW_FLOOR per gene, per cell for a learned `ϕxy_locs`.  No float32-oracle clause: the caller's data keep every element off
+    the relu kink (asserted here for the velocity models: z >= LIT_Z_MIN at `params` / `eps`), and tests/test_cell_rows_cpu.py holds
+    the float32 oracle's own rows to <= 0.25 of this bar on lit_cell_problem's data, where one cell left out, counted twice or
+    evaluated with its neighbour's record moves a row by several bars.  Returns {block: worst err / bar} for the caller to print."""
+    p64 = problem_from_spec(spec, torch.float64)
+    par = {n: v.detach().cpu().double() for n, v in params.items()}
+    e64 = {k: v.detach().cpu().double() for k, v in eps.items() if not k.startswith("_")}
+    if p64.kind == "velocity":
+        zmin = lit_z_min(p64, par, e64)
+        assert zmin >= LIT_Z_MIN, (label, zmin)
+    _, g64, _, _ = orc.loss_and_grads(p64, par, e64)
+    ratio = gene_row_ratios(gene_row_blocks(grads, spec), gene_row_blocks(g64, spec))
+    bad = [(k, int(g), float(v[g])) for k, v in ratio.items() for g in np.nonzero(v > 1.0)[0]]
+    assert not bad, (label, bad[:12], len(bad))
+    return {k: float(v.max()) for k, v in ratio.items()}
 
 
 # how often assert_step_matches_oracle's second clause (<= 4 x the float32 oracle's own error) was what let a gradient block pass;
