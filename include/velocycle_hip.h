@@ -35,6 +35,9 @@
  *   vc_phase_mle                Phases.from_cycle_mle (phases.py:471-509): the log-likelihood of every cell's spliced counts
  *                               on a grid of phases (ElogS / exp / Poisson | GammaPoisson log_prob / sum over genes, :499-507)
  *                               and its arg-max per cell (:508); stand-alone, no engine
+ *   vc_gene_glm                 no counterpart (a host loop of one GLM per gene would be it): the model of Phases.from_cycle_mle
+ *                               (phases.py:487-507) solved for the gene harmonics with the phases known -- a Poisson or
+ *                               negative-binomial log-link regression on the Fourier design per gene; stand-alone, no engine
  *   vc_pca_stage, vc_pca_apply  Phases.from_pca_heuristic (phases.py:307-382): np.log(layer + small_count) and the one large
  *                               operation of a block power iteration that replaces sklearn's PCA(n_components).fit_transform
  *                               (:343-349); stand-alone, no engine
@@ -494,6 +497,55 @@ int vc_expected_logs(vc_engine* e, const float* nu, const float* dnu, const floa
 int vc_phase_mle(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* T_dev,
                  const float* expT_dev, int bins, const float* m_dev, int noise, const float* r_dev, int32_t* best_bin_dev,
                  float* logp_rel_dev, void* hip_stream);
+
+/* --- per-gene harmonic regression given the phases (stand-alone: no engine handle) -------------------------------------------
+ * The model of Phases.from_cycle_mle (phases.py:487-507), mu_gc = exp(nu_g . zeta(phi_c)) n_c^a, solved for nu with the phases known:
+ * one Poisson or negative-binomial log-link regression on a Fourier design per gene, by a damped Newton iteration that runs inside
+ * the kernel (one workgroup per gene, one launch, no workspace, no allocation, no synchronisation; asynchronous on hip_stream).
+ * Every pointer is DEVICE memory.
+ *   counts_dev      element (g, c) at index g * gene_stride + c (gene_stride >= Nc); float (VC_COUNTS_F32) or uint16_t (VC_COUNTS_U16)
+ *   basis_dev       float[K][Nc], K = 2 H + 1 in {1, 3, 5, 7}: rows [1, sin phi, cos phi, sin 2 phi, ...] (utils.torch_fourier_basis);
+ *                   row 0 is taken to be 1 and is not read
+ *   logm_dev        float[Nc]: a log n_c (phases.py:492-494), the offset of eta = nu . basis[:, c] + logm[c]
+ *   noise           VC_NOISE_POISSON | VC_NOISE_NB; VC_NOISE_LOGNORMAL returns VC_ERR_UNSUPPORTED
+ *   r_dev           float[Ng] > 0: 1 / dispersion per gene; NULL for Poisson
+ *   prior_mean_dev, prior_prec_dev   both NULL (maximum likelihood), or double[Ng][K] each: a Gaussian prior per coefficient, its
+ *                   penalty sum_i prec_i (nu_i - mean_i)^2 / 2 taken off the objective; a coefficient whose mean is not finite or
+ *                   whose precision is not a positive finite number has none
+ *   tol, max_iter   stop at the Newton decrement g' H^-1 g <= tol (>= 0), after at most max_iter (>= 1) steps
+ * Objective (the part of the log-likelihood that depends on nu), mu = exp(eta):
+ *   Poisson  sum_c k eta - mu         NB  sum_c k ln(mu / (r + mu)) - r ln((r + mu) / r)  =  sum_c k eta - (k + r) ln(r + mu)  +  Nc r ln r
+ * (the negative binomial's r ln r is inside, so that every term has the size of a log-probability); the Hessian is the observed one,
+ * w = mu | mu r (k + r) / (r + mu)^2, with the prior precisions on its diagonal.  Start: nu_0 = ln(sum k / sum e^logm), harmonics 0
+ * (with a prior: its means, except nu_0).  Per-element arithmetic is float32 (eta itself is formed in float64 from the float32 tables),
+ * every sum float64 in a fixed order, the K x K algebra float64: identical bits under repetition, uint16 or float32 storage, and any
+ * cutting of the genes into calls.  Outputs, per gene, of the last accepted point:
+ *   nu_dev          double[Ng][K]
+ *   cov_dev         double[Ng][K (K + 1) / 2]: H^-1, lower triangle packed row by row ((i, j), j <= i, at i (i + 1) / 2 + j); NaN when SINGULAR
+ *   loglik_dev      double[Ng]: the objective above, without the prior term
+ *   dec_dev         double[Ng]: the last Newton decrement;  iterations_dev int32[Ng]: Newton steps taken
+ *   status_dev      int32[Ng]:
+ *     VC_GLM_CONVERGED  dec <= tol
+ *     VC_GLM_ROUNDING   the gradient cannot be told from its float32 rounding: every |g_i| <= 4 eps32 sqrt(sum_c (w_c^2 + res_c^2) B_ic^2),
+ *                       res the residual k - mu | (k - mu) r / (r + mu) (a relative error e of mu moves res by w e; res itself rounds by
+ *                       |res| e).  At counts of 10^4 this floor of dec lies above a tol of 1e-10
+ *     VC_GLM_UNBOUNDED  a step would take a harmonic coefficient out of [-50, 50] (separation: no finite maximum), or the gene has no
+ *                       count at all; nu is the last point inside (no count: nu_0 = -inf, the other outputs NaN)
+ *     VC_GLM_SINGULAR   the Cholesky factorisation of the Hessian failed (a pivot <= 0 or not finite)
+ *     VC_GLM_MAX_ITER   max_iter steps were taken, or the gene used up its 30 step halvings (a step is halved while the objective drops
+ *                       by more than its own float32 rounding, 8 eps32 sum |terms|)
+ * A gene's status touches no other gene's outputs; every path is bounded.  VC_ERR_ARG (NULL input or output, K not in {1, 3, 5, 7},
+ * Nc < 1, Ng < 1, gene_stride < Nc, max_iter < 1, tol < 0, one prior pointer without the other, NB without r_dev), VC_ERR_UNSUPPORTED
+ * (Lognormal): all decided before anything is launched.  Errors: vc_last_error(NULL). */
+#define VC_GLM_CONVERGED 0
+#define VC_GLM_ROUNDING 1
+#define VC_GLM_UNBOUNDED 2
+#define VC_GLM_SINGULAR 3
+#define VC_GLM_MAX_ITER 4
+int vc_gene_glm(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* basis_dev, int K,
+                const float* logm_dev, int noise, const float* r_dev, const double* prior_mean_dev, const double* prior_prec_dev,
+                double tol, int max_iter, double* nu_dev, double* cov_dev, double* loglik_dev, double* dec_dev,
+                int32_t* iterations_dev, int32_t* status_dev, void* hip_stream);
 
 /* --- PCA phase prior (Phases.from_pca_heuristic, phases.py:307-382): staging and the power iteration's pass ------------------
  * Stand-alone (no engine); the iteration itself (QR, Rayleigh-Ritz on 8 x 8 matrices, float64) is the caller's:

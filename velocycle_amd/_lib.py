@@ -22,6 +22,7 @@ MODEL = {"phase": 0, "velocity": 1}
 GUIDE = {"meanfield": 0, "lrmn": 1}
 NOISE = {"NegativeBinomial": 0, "Poisson": 1, "Lognormal": 2}
 VC_COUNTS_F32, VC_COUNTS_U16 = 0, 1
+VC_GLM_CONVERGED, VC_GLM_ROUNDING, VC_GLM_UNBOUNDED, VC_GLM_SINGULAR, VC_GLM_MAX_ITER = 0, 1, 2, 3, 4
 
 # sample sites, parameters and eps blocks, named as in the reference
 SITES = ["ϕxy", "ν", "Δν", "shape_inv", "logγg", "logβg", "νω", "rho_real"]
@@ -132,6 +133,9 @@ EXPORTS = {
                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vc_phase_mle": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vc_gene_glm": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p]),
     "vc_pca_stage": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p]),
     "vc_pca_apply_workspace": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),

@@ -132,6 +132,46 @@ class Cycle(_HarmonicTable):
         out.stds = pd.DataFrame(np.broadcast_to(stds, (nrow, len(gene_names))).copy(), index=rows, columns=gene_names)
         return out
 
+    @classmethod
+    def from_phases_mle(cls, phases, data, harmonics=1, a=1, noisemodel='Poisson', dispersion=0.3, *, layer='spliced', prior=None,
+                        return_fit=False, **worker_kw):
+        """The cycle of every gene of `data` given the cells' `phases`: the model of `Phases.from_cycle_mle`
+        (mu = exp(nu . zeta(phi)) n_scounts^a, Poisson or NegativeBinomial; reference phases.py:487-507) solved for the gene harmonics,
+        one log-link regression on the Fourier design per gene, by the HIP kernel behind `velocycle_amd.gene_harmonics.gene_harmonics`.
+        means = the maximum-likelihood coefficients (with `prior`, a Cycle over the same genes and harmonics: the posterior modes under
+        its Gaussians), stds = sqrt of the diagonal of the inverse observed Hessian.  `dispersion` may be one value per gene; the layer may
+        be dense or sparse.  Keyword-only: `layer`, `prior`, `return_fit=True` returns (Cycle, GeneHarmonicFit) -- the fit holds the
+        log-likelihoods, the likelihood-ratio statistic for periodicity and its p-value, and how every gene's iteration ended; anything
+        else goes to the worker (tol, max_iter, device, chunk_genes, storage)."""
+        from .gene_harmonics import NOISEMODELS, gene_harmonics
+        if noisemodel not in NOISEMODELS:
+            raise NotImplementedError("Not implemented yet, sorry")
+        if layer not in data.layers:
+            raise ValueError(f"{layer=} is not a layer of the data")
+        counts = data.layers[layer]
+        Nc, Ng = counts.shape
+        cells_p, cells_d = list(phases.phi_xy.columns), list(data.obs.index)
+        named = not isinstance(phases.phi_xy.columns, pd.RangeIndex)
+        if phases.phi_xy.shape[1] != Nc or (named and cells_p != cells_d):
+            raise ValueError("the cells of the phases do not match the cells of the data (same cells, same order)")
+        genes = list(data.var.index)
+        prior_means = prior_stds = None
+        if prior is not None:
+            named = not isinstance(prior.means.columns, pd.RangeIndex)
+            if prior.means.shape[1] != Ng or (named and list(prior.means.columns) != genes):
+                raise ValueError("the genes of the prior do not match the genes of the data (same genes, same order)")
+            if prior.harmonics != harmonics:
+                raise ValueError(f"the prior has {prior.harmonics} harmonics, the fit {harmonics}")
+            prior_means = np.asarray(prior.means.values, dtype=np.float64)
+            prior_stds = np.asarray(prior.stds.values, dtype=np.float64)
+        if not (hasattr(counts, "tocsr") or torch.is_tensor(counts)):
+            counts = np.asarray(counts)
+        fit = gene_harmonics(counts, np.asarray(phases.phi_xy.values, dtype=np.float64), np.asarray(data.obs.n_scounts.values),
+                             harmonics=harmonics, a=a, noisemodel=noisemodel, dispersion=dispersion, prior_means=prior_means,
+                             prior_stds=prior_stds, **worker_kw)
+        out = cls.from_array(fit.means, fit.stds, gene_names=data.var.index)
+        return (out, fit) if return_fit else out
+
 
 def reorder(cycle: Cycle, gene_list):
     return Cycle.from_array(means_array=cycle.means[gene_list], stds_array=cycle.stds[gene_list])

@@ -1,0 +1,421 @@
+// Per-gene harmonic regression given the cells' phases: vc_gene_glm of include/velocycle_hip.h, the model of Phases.from_cycle_mle
+// (reference velocycle/phases.py:487-507, utils.torch_fourier_basis) solved for the other factor.  Stand-alone: no engine, no
+// workspace, one launch; the whole damped Newton iteration of a gene runs inside its workgroup.
+//
+// Per gene g:  maximise over nu (K = 2H+1 coefficients)
+//   Poisson            sum_c k eta - mu                                eta_c = nu . B[:, c] + logm_c,   mu = exp(eta)
+//   negative binomial  sum_c k eta - (k + r) ln(r + mu)  (+ Nc r ln r: formed as k d - r w, d = eta - ln(r + mu), w = ln(r + mu) - ln r)
+//   minus              sum_i prec_i (nu_i - m_i)^2 / 2                 (optional Gaussian prior)
+// Gradient  sum_c res B_i,  res = k - mu | (k - mu) r / (r + mu);  observed Hessian  sum_c w B_i B_j,  w = mu | mu r (k + r) / (r + mu)^2,
+// prior precisions on its diagonal.  Both objectives are concave.
+//
+// Mapping: one workgroup of GLM_NW waves per gene, its lanes walk the gene's row of the [genes][cells] block with stride 256 (every wave
+// instruction reads 64 consecutive cells: coalesced).  Per element: eta in float64 from the float32 tables and the float64 nu (K fmas),
+// mu = 2^n 2^f with one v_exp_f32 on the fraction (mu carries one rounding whatever |eta|), the residual, the weight and the logarithm
+// in float32.  Sums: every lane accumulates in float64 (products with B are exact there), the lanes of a wave are folded by a fixed
+// shuffle tree, the waves added in wave order through the LDS -- no atomics, identical bits on repetition.  After the fold every lane
+// holds the same totals and runs the same float64 K x K algebra (Cholesky, step, tests), so the control flow is uniform by construction
+// and nothing has to be broadcast.
+//
+// Iteration (status codes: velocycle_hip.h):
+//   start    nu0 = ln(sum k / sum e^logm), harmonics 0 (prior means where finite, except nu0)
+//   at nu    g, H, objective L, A = sum |terms of L|, N_i = sum (w^2 + res^2) B_i^2
+//            Cholesky of H fails (pivot <= 0 or not finite)          -> SINGULAR
+//            dec = g' H^-1 g <= tol                                    -> CONVERGED
+//            every |g_i| <= 4 eps32 sqrt(N_i)                          -> ROUNDING   (the gradient is its own float32 rounding:
+//                                                                         a relative error e of mu moves res by w e, res rounds by |res| e)
+//            steps taken == max_iter                                   -> MAX_ITER
+//   step     nu' = nu + t H^-1 g, t = 1; a harmonic of nu' outside [-50, 50] -> UNBOUNDED (nu stays the last point inside)
+//            accepted unless L' < L - 8 eps32 max(A, A') (a drop beyond the objective's own rounding), else t /= 2; a gene has
+//            GLM_MAX_HALVINGS halvings in all (then MAX_ITER): no path spins.
+// Outputs are those of the last accepted point: nu, packed H^-1, L without the prior term, dec, steps taken, status.
+#include <string>
+
+#include "vc_common.h"
+
+void vc_set_global_error(const char* msg);      // vc_engine.hip: the message vc_last_error(NULL) returns
+
+// every product-sum is written as the fma it is meant to be; nothing else may be contracted (the same operations in every instantiation)
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int GLM_NW = 4;                 // waves per workgroup
+constexpr int GLM_NT = GLM_NW * 64;
+constexpr int GLM_MAX_HALVINGS = 30;
+constexpr double GLM_EPS32 = 1.1920928955078125e-07;
+constexpr double GLM_LOG2E = 1.4426950408889634;
+constexpr double GLM_BOUND = 50.0;
+
+template <bool U16>
+__device__ __forceinline__ float glm_count(const void* row, long long c) {
+  if (U16) return (float)((const unsigned short*)row)[c];
+  return ((const float*)row)[c];
+}
+
+// acc[i] := the sum of acc[i] over the workgroup, in every lane: shuffle tree over the wave, then the waves in wave order
+template <int N>
+__device__ __forceinline__ void glm_fold(double (&acc)[N], double (*part)[N], double* tot, int lane, int wave) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double v = acc[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) part[wave][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    double s = part[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < GLM_NW; ++w) s += part[w][threadIdx.x];
+    tot[threadIdx.x] = s;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < N; ++i) acc[i] = tot[i];
+}
+
+// index of (i, j), j <= i, in the packed lower triangle
+__device__ __host__ constexpr int glm_tri(int i, int j) { return i * (i + 1) / 2 + j; }
+
+template <int H>
+struct GlmSums {
+  static constexpr int K = 2 * H + 1;
+  static constexpr int NH = K * (K + 1) / 2;
+  static constexpr int OFF_H = K, OFF_L = K + NH, OFF_A = OFF_L + 1, OFF_N = OFF_A + 1, N = OFF_N + K;
+};
+
+// One pass over the gene's cells at nu: acc = [g (K) | H packed (NH) | L | A | N (K)], folded over the workgroup
+template <int H, int NOISE, bool U16>
+__device__ __forceinline__ void glm_pass(const void* __restrict__ row, long long Nc, const float* __restrict__ B,
+                                         const float* __restrict__ logm, float r, double lnr, const double (&nu)[2 * H + 1],
+                                         double (&acc)[GlmSums<H>::N], double (*part)[GlmSums<H>::N], double* tot, int lane, int wave) {
+  typedef GlmSums<H> S;
+  constexpr int K = S::K;
+#pragma unroll
+  for (int i = 0; i < S::N; ++i) acc[i] = 0.0;
+  for (long long c = threadIdx.x; c < Nc; c += GLM_NT) {
+    const float k = glm_count<U16>(row, c);
+    double b[K];
+    b[0] = 1.0;
+#pragma unroll
+    for (int i = 1; i < K; ++i) b[i] = (double)B[(long long)i * Nc + c];
+    double eta = (double)logm[c] + nu[0];
+#pragma unroll
+    for (int i = 1; i < K; ++i) eta = __builtin_fma(nu[i], b[i], eta);
+    // mu = 2^n 2^f: the fraction is exact in float64 and rounds once to float32; beyond 2^120 the step is refused by its objective
+    double t = eta * GLM_LOG2E;
+    t = t > 120.0 ? 120.0 : (t < -140.0 ? -140.0 : t);
+    const double tn = __builtin_rint(t);
+    const float mu = __builtin_ldexpf(__builtin_amdgcn_exp2f((float)(t - tn)), (int)tn);
+    const double kd = (double)k;
+    float res, w;
+    double term, mag;
+    if (NOISE == VC_NOISE_NB) {
+      const float s = r + mu;
+      const float rs = __builtin_amdgcn_rcpf(s);
+      const float p = r * rs;                                       // r / (r + mu)
+      res = (k - mu) * p;
+      w = (mu * rs) * p * (k + r);
+      // ln(r + mu) = max(eta, ln r) + ln(1 + x), x = min(mu, r) / max(mu, r): the large part is exact in float64, the float32
+      // logarithm is taken of a number in [1, 2], so d and w lose nothing to the size of eta (counts of 10^4: (k + r) ln(r + mu) ~ 10^5)
+      const bool big = mu >= r;
+      const float x = (big ? r : mu) * __builtin_amdgcn_rcpf(big ? mu : r);
+      const double lg = (double)(VC_LN2 * __builtin_amdgcn_logf(1.f + x));
+      const double e = eta - lnr;
+      const double d = big ? -lg : e - lg;                          // eta - ln(r + mu)
+      const double wl = big ? e + lg : lg;                          // ln(r + mu) - ln r
+      const double ls = (big ? eta : lnr) + lg;
+      const double kr = (double)(k + r);
+      term = __builtin_fma(kd, d, -(double)r * wl);
+      mag = __builtin_fma(kr, __builtin_fabs(ls), __builtin_fabs(kd * eta));
+    } else {
+      res = k - mu;
+      w = mu;
+      term = __builtin_fma(kd, eta, -(double)mu);
+      mag = __builtin_fabs(kd * eta) + (double)mu;
+    }
+    const double rd = (double)res, wd = (double)w;
+    const double n2 = __builtin_fma(wd, wd, rd * rd);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      acc[i] = __builtin_fma(rd, b[i], acc[i]);
+      const double wb = wd * b[i];
+#pragma unroll
+      for (int j = 0; j <= i; ++j) acc[S::OFF_H + glm_tri(i, j)] = __builtin_fma(wb, b[j], acc[S::OFF_H + glm_tri(i, j)]);
+      acc[S::OFF_N + i] = __builtin_fma(n2, b[i] * b[i], acc[S::OFF_N + i]);
+    }
+    acc[S::OFF_L] += term;
+    acc[S::OFF_A] += mag;
+  }
+  glm_fold<S::N>(acc, part, tot, lane, wave);
+}
+
+// In-place Cholesky of the packed lower triangle (float64); false if a pivot is not a positive finite number
+template <int K>
+__device__ __forceinline__ bool glm_chol(double (&a)[K * (K + 1) / 2]) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    double d = a[glm_tri(j, j)];
+#pragma unroll
+    for (int q = 0; q < j; ++q) d = __builtin_fma(-a[glm_tri(j, q)], a[glm_tri(j, q)], d);
+    ok = ok && d > 0.0 && d < 1.0e300;
+    const double l = __builtin_sqrt(ok ? d : 1.0);
+    a[glm_tri(j, j)] = l;
+    const double il = 1.0 / l;
+#pragma unroll
+    for (int i = j + 1; i < K; ++i) {
+      double s = a[glm_tri(i, j)];
+#pragma unroll
+      for (int q = 0; q < j; ++q) s = __builtin_fma(-a[glm_tri(i, q)], a[glm_tri(j, q)], s);
+      a[glm_tri(i, j)] = s * il;
+    }
+  }
+  return ok;
+}
+
+// x := (L L')^-1 x
+template <int K>
+__device__ __forceinline__ void glm_solve(const double (&l)[K * (K + 1) / 2], double (&x)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    double s = x[i];
+#pragma unroll
+    for (int q = 0; q < i; ++q) s = __builtin_fma(-l[glm_tri(i, q)], x[q], s);
+    x[i] = s / l[glm_tri(i, i)];
+  }
+#pragma unroll
+  for (int i = K - 1; i >= 0; --i) {
+    double s = x[i];
+#pragma unroll
+    for (int q = i + 1; q < K; ++q) s = __builtin_fma(-l[glm_tri(q, i)], x[q], s);
+    x[i] = s / l[glm_tri(i, i)];
+  }
+}
+
+// Gradient gr, Cholesky factor of the Hessian and penalty of the penalised objective at nu, from the sums of a pass
+template <int H>
+__device__ __forceinline__ bool glm_factor(const double (&acc)[GlmSums<H>::N], const double (&nu)[2 * H + 1], const double (&pm)[2 * H + 1],
+                                           const double (&pp)[2 * H + 1], double (&gr)[2 * H + 1],
+                                           double (&chol)[GlmSums<H>::NH], double& pen) {
+  typedef GlmSums<H> S;
+  pen = 0.0;
+#pragma unroll
+  for (int i = 0; i < S::NH; ++i) chol[i] = acc[S::OFF_H + i];
+#pragma unroll
+  for (int i = 0; i < S::K; ++i) {
+    const double d = nu[i] - pm[i];
+    gr[i] = __builtin_fma(-pp[i], d, acc[i]);
+    chol[glm_tri(i, i)] += pp[i];
+    pen = __builtin_fma(0.5 * pp[i] * d, d, pen);
+  }
+  return glm_chol<S::K>(chol);
+}
+
+template <int H, int NOISE, bool U16>
+__global__ __launch_bounds__(GLM_NT) void vc_gene_glm_kernel(const void* __restrict__ counts, long long Nc, long long gene_stride,
+                                                             const float* __restrict__ B, const float* __restrict__ logm,
+                                                             const float* __restrict__ rg, const double* __restrict__ prior_mean,
+                                                             const double* __restrict__ prior_prec, double tol, int max_iter,
+                                                             double* __restrict__ nu_out, double* __restrict__ cov_out,
+                                                             double* __restrict__ loglik_out, double* __restrict__ dec_out,
+                                                             int* __restrict__ iter_out, int* __restrict__ status_out) {
+  typedef GlmSums<H> S;
+  constexpr int K = S::K, NH = S::NH;
+  __shared__ double part[GLM_NW][S::N];
+  __shared__ double tot[S::N];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const long long g = blockIdx.x;
+  const void* row = U16 ? (const void*)((const unsigned short*)counts + g * gene_stride) : (const void*)((const float*)counts + g * gene_stride);
+  const float r = NOISE == VC_NOISE_NB ? rg[g] : 0.f;
+  const double lnr = NOISE == VC_NOISE_NB ? log((double)r) : 0.0;
+
+  // the prior of this gene: a coefficient has one where its mean is finite and its precision a positive finite number
+  double pm[K], pp[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    pm[i] = 0.0;
+    pp[i] = 0.0;
+    if (prior_mean) {
+      const double m = prior_mean[g * K + i], p = prior_prec[g * K + i];
+      if (__builtin_fabs(m) < 1.0e300 && p > 0.0 && p < 1.0e300) { pm[i] = m; pp[i] = p; }
+    }
+  }
+
+  // start: sum k and sum e^logm
+  double nu[K];
+  {
+    double s2[2] = {0.0, 0.0};
+    for (long long c = threadIdx.x; c < Nc; c += GLM_NT) {
+      s2[0] += (double)glm_count<U16>(row, c);
+      s2[1] += (double)__builtin_amdgcn_exp2f(VC_LOG2E * logm[c]);
+    }
+    glm_fold<2>(s2, (double(*)[2])(void*)&part[0][0], tot, lane, wave);
+    __syncthreads();                                               // part / tot are used with another row length below
+    nu[0] = log(s2[0] / s2[1]);
+#pragma unroll
+    for (int i = 1; i < K; ++i) nu[i] = pp[i] > 0.0 ? pm[i] : 0.0;
+    if (!(s2[0] > 0.0) || !(__builtin_fabs(nu[0]) < 1.0e300)) {    // no count at all (or no finite scale): no maximum
+      if (threadIdx.x == 0) {
+        const double nan = __builtin_nan("");
+        for (int i = 0; i < K; ++i) nu_out[g * K + i] = i == 0 ? nu[0] : 0.0;
+        for (int i = 0; i < NH; ++i) cov_out[g * NH + i] = nan;
+        loglik_out[g] = nan;
+        dec_out[g] = nan;
+        iter_out[g] = 0;
+        status_out[g] = VC_GLM_UNBOUNDED;
+      }
+      return;
+    }
+  }
+
+  double acc[S::N];
+  glm_pass<H, NOISE, U16>(row, Nc, B, logm, r, lnr, nu, acc, part, tot, lane, wave);
+  int status = VC_GLM_MAX_ITER, steps = 0, halvings = GLM_MAX_HALVINGS;
+  double dec = __builtin_nan(""), Lcur = 0.0;
+  double chol[NH];
+  bool have_chol = false;
+  for (;;) {
+    // acc holds the sums at nu; only L and A of them outlive the next pass (the step is retried from nu, gr and dx)
+    Lcur = acc[S::OFF_L];
+    const double Acur = acc[S::OFF_A];
+    double gr[K], pen;
+    have_chol = glm_factor<H>(acc, nu, pm, pp, gr, chol, pen);
+    if (!have_chol) { status = VC_GLM_SINGULAR; break; }
+    double dx[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) dx[i] = gr[i];
+    glm_solve<K>(chol, dx);
+    dec = 0.0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) dec = __builtin_fma(gr[i], dx[i], dec);
+    if (!(__builtin_fabs(dec) < 1.0e300)) { status = VC_GLM_SINGULAR; have_chol = false; break; }
+    if (dec <= tol) { status = VC_GLM_CONVERGED; break; }
+    bool noise = true;
+#pragma unroll
+    for (int i = 0; i < K; ++i) noise = noise && __builtin_fabs(gr[i]) <= 4.0 * GLM_EPS32 * __builtin_sqrt(acc[S::OFF_N + i]);
+    if (noise) { status = VC_GLM_ROUNDING; break; }
+    if (steps >= max_iter) { status = VC_GLM_MAX_ITER; break; }
+    const double Lpen = Lcur - pen;
+    double t = 1.0;
+    bool moved = false, overwritten = false;
+    for (;;) {
+      double trial[K];
+      bool inside = true;
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        trial[i] = __builtin_fma(t, dx[i], nu[i]);
+        if (i > 0) inside = inside && __builtin_fabs(trial[i]) <= GLM_BOUND;
+      }
+      if (!inside) { status = VC_GLM_UNBOUNDED; break; }
+      glm_pass<H, NOISE, U16>(row, Nc, B, logm, r, lnr, trial, acc, part, tot, lane, wave);
+      overwritten = true;
+      double pen2 = 0.0;
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        const double d = trial[i] - pm[i];
+        pen2 = __builtin_fma(0.5 * pp[i] * d, d, pen2);
+      }
+      const double A = acc[S::OFF_A] > Acur ? acc[S::OFF_A] : Acur;
+      if (acc[S::OFF_L] - pen2 >= Lpen - 8.0 * GLM_EPS32 * A) {      // false for a NaN: such a step is halved
+#pragma unroll
+        for (int i = 0; i < K; ++i) nu[i] = trial[i];
+        moved = true;
+        break;
+      }
+      if (halvings == 0) { status = VC_GLM_MAX_ITER; break; }
+      --halvings;
+      t *= 0.5;
+    }
+    if (!moved) {
+      if (overwritten) {                                             // a refused trial's sums are in acc: form those of nu again
+        glm_pass<H, NOISE, U16>(row, Nc, B, logm, r, lnr, nu, acc, part, tot, lane, wave);
+        Lcur = acc[S::OFF_L];
+        have_chol = glm_factor<H>(acc, nu, pm, pp, gr, chol, pen);
+      }
+      break;
+    }
+    ++steps;
+  }
+
+  // the covariance H^-1 of the last accepted point, column by column from the factor
+  double cov[NH];
+  if (have_chol) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      double e[K];
+#pragma unroll
+      for (int i = 0; i < K; ++i) e[i] = i == j ? 1.0 : 0.0;
+      glm_solve<K>(chol, e);
+#pragma unroll
+      for (int i = j; i < K; ++i) cov[glm_tri(i, j)] = e[i];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NH; ++i) cov[i] = __builtin_nan("");
+  }
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) nu_out[g * K + i] = nu[i];
+#pragma unroll
+    for (int i = 0; i < NH; ++i) cov_out[g * NH + i] = cov[i];
+    loglik_out[g] = Lcur;
+    dec_out[g] = dec;
+    iter_out[g] = steps;
+    status_out[g] = status;
+  }
+}
+
+int glm_fail(int code, const char* msg) {
+  vc_set_global_error(msg);
+  return code;
+}
+
+}  // namespace
+
+extern "C" int vc_gene_glm(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* basis_dev,
+                           int K, const float* logm_dev, int noise, const float* r_dev, const double* prior_mean_dev,
+                           const double* prior_prec_dev, double tol, int max_iter, double* nu_dev, double* cov_dev, double* loglik_dev,
+                           double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, void* hip_stream) {
+  if (noise == VC_NOISE_LOGNORMAL) return glm_fail(VC_ERR_UNSUPPORTED, "vc_gene_glm: Lognormal noise is not implemented (Poisson or NegativeBinomial)");
+  if (noise != VC_NOISE_NB && noise != VC_NOISE_POISSON) return glm_fail(VC_ERR_ARG, "vc_gene_glm: noise must be VC_NOISE_POISSON or VC_NOISE_NB");
+  if (count_kind != VC_COUNTS_F32 && count_kind != VC_COUNTS_U16) return glm_fail(VC_ERR_ARG, "vc_gene_glm: count_kind must be VC_COUNTS_F32 or VC_COUNTS_U16");
+  if (K != 1 && K != 3 && K != 5 && K != 7) return glm_fail(VC_ERR_ARG, "vc_gene_glm: K must be 1, 3, 5 or 7 (2 H + 1, H in 0..3)");
+  if (Ng < 1 || Nc < 1) return glm_fail(VC_ERR_ARG, "vc_gene_glm: Ng and Nc must be >= 1");
+  if (Ng > 0x7fffffffLL) return glm_fail(VC_ERR_ARG, "vc_gene_glm: more than 2^31 - 1 genes in one call");
+  if (gene_stride < Nc) return glm_fail(VC_ERR_ARG, "vc_gene_glm: gene_stride < Nc");
+  if (max_iter < 1) return glm_fail(VC_ERR_ARG, "vc_gene_glm: max_iter must be >= 1");
+  if (!(tol >= 0.0)) return glm_fail(VC_ERR_ARG, "vc_gene_glm: tol must be >= 0");
+  if (!counts_dev || !basis_dev || !logm_dev) return glm_fail(VC_ERR_ARG, "vc_gene_glm: null input pointer");
+  if (!nu_dev || !cov_dev || !loglik_dev || !dec_dev || !iterations_dev || !status_dev) return glm_fail(VC_ERR_ARG, "vc_gene_glm: null output pointer");
+  if (noise == VC_NOISE_NB && !r_dev) return glm_fail(VC_ERR_ARG, "vc_gene_glm: the negative binomial needs r_dev (1 / dispersion per gene)");
+  if ((prior_mean_dev == nullptr) != (prior_prec_dev == nullptr)) return glm_fail(VC_ERR_ARG, "vc_gene_glm: the prior needs both its means and its precisions");
+  const dim3 grid((unsigned)Ng), block(GLM_NT);
+  hipStream_t st = (hipStream_t)hip_stream;
+#define GLM_LAUNCH(H, NOISE, U16)                                                                                                      \
+  hipLaunchKernelGGL((vc_gene_glm_kernel<H, NOISE, U16>), grid, block, 0, st, counts_dev, (long long)Nc, (long long)gene_stride,       \
+                     basis_dev, logm_dev, r_dev, prior_mean_dev, prior_prec_dev, tol, max_iter, nu_dev, cov_dev, loglik_dev, dec_dev,  \
+                     (int*)iterations_dev, (int*)status_dev)
+#define GLM_LAUNCH_H(H)                                                                                                               \
+  do {                                                                                                                                \
+    if (noise == VC_NOISE_NB) { if (u16) GLM_LAUNCH(H, VC_NOISE_NB, true); else GLM_LAUNCH(H, VC_NOISE_NB, false); }                     \
+    else { if (u16) GLM_LAUNCH(H, VC_NOISE_POISSON, true); else GLM_LAUNCH(H, VC_NOISE_POISSON, false); }                                \
+  } while (0)
+  const bool u16 = count_kind == VC_COUNTS_U16;
+  switch (K) {
+    case 1: GLM_LAUNCH_H(0); break;
+    case 3: GLM_LAUNCH_H(1); break;
+    case 5: GLM_LAUNCH_H(2); break;
+    default: GLM_LAUNCH_H(3); break;
+  }
+#undef GLM_LAUNCH_H
+#undef GLM_LAUNCH
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    try { vc_set_global_error((std::string("vc_gene_glm: launch failed: ") + hipGetErrorString(err)).c_str()); } catch (...) {}
+    return VC_ERR_HIP;
+  }
+  return VC_OK;
+}
