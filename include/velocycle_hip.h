@@ -38,6 +38,9 @@
  *   vc_gene_glm                 no counterpart (a host loop of one GLM per gene would be it): the model of Phases.from_cycle_mle
  *                               (phases.py:487-507) solved for the gene harmonics with the phases known -- a Poisson or
  *                               negative-binomial log-link regression on the Fourier design per gene; stand-alone, no engine
+ *   vc_gene_dispersion          no counterpart (the reference learns shape_inv only inside the SVI, velocity_inference_model.py:383):
+ *                               the maximum-likelihood (or Gamma-prior mode) negative-binomial dispersion per gene with the means of
+ *                               vc_gene_glm known; stand-alone, no engine
  *   vc_pca_stage, vc_pca_apply  Phases.from_pca_heuristic (phases.py:307-382): np.log(layer + small_count) and the one large
  *                               operation of a block power iteration that replaces sklearn's PCA(n_components).fit_transform
  *                               (:343-349); stand-alone, no engine
@@ -546,6 +549,50 @@ int vc_gene_glm(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, 
                 const float* logm_dev, int noise, const float* r_dev, const double* prior_mean_dev, const double* prior_prec_dev,
                 double tol, int max_iter, double* nu_dev, double* cov_dev, double* loglik_dev, double* dec_dev,
                 int32_t* iterations_dev, int32_t* status_dev, void* hip_stream);
+
+/* --- per-gene negative-binomial dispersion given the means (stand-alone: no engine handle) -----------------------------------
+ * The third factor of the model of vc_gene_glm: with eta_c = nu_g . basis[:, c] + logm[c], mu = exp(eta) known, maximise over
+ * rho = ln r (r = 1 / dispersion = 1 / shape_inv) the r-dependent log-likelihood of the gene
+ *   L(rho) = sum_c lgamma(k + r) - lgamma(r) + k (eta - ln(r + mu)) - r (ln(r + mu) - ln r)         (L + sum_c -lgamma(k + 1) is the whole)
+ * plus, with a prior shape_inv ~ Gamma(alpha, beta) (velocity_inference_model.py:383), -(alpha - 1) rho - beta e^-rho: f(rho).
+ * One workgroup per gene, one launch, no workspace, no allocation, no synchronisation; asynchronous on hip_stream.  Every pointer is
+ * DEVICE memory.  counts_dev, count_kind, Ng, Nc, gene_stride, basis_dev, K, logm_dev: as for vc_gene_glm (counts are taken to be
+ * integers; Nc <= 2^31 - 1).
+ *   nu_dev          double[Ng][K]: the coefficients (vc_gene_glm's nu_dev)
+ *   r_start_dev     float[Ng] or NULL: where the iteration starts; NULL: the moment estimate sum mu^2 / sum((k - mu)^2 - mu)
+ *   prior_alpha_dev, prior_beta_dev   both NULL, or double[Ng] each; a gene whose alpha or beta is not a positive finite number has none
+ *   tol, max_iter   stop at f'^2 / -f'' <= tol (>= 0) after at most max_iter steps; max_iter == 0 evaluates at r_start_dev only
+ * mu is formed exactly as in vc_gene_glm (eta float64, one float32 exp2); everything that depends on r is float64, every sum float64
+ * in a fixed order; the gamma terms come from the histogram of the counts (sum_c psi(k + r) - psi(r) = sum_j #{k > j} / (r + j)).
+ * rho is confined to [VC_DISP_RHO_MIN, VC_DISP_RHO_MAX] = [ln 1e-3, ln 1e6].  With
+ *   noise = 4 eps32 sqrt(sum_c [r mu (k - mu) / (r + mu)^2]^2) + 64 eps64 r sum_c |parts of dL/dr|
+ * (what one float32 rounding of mu does to f', and the float64 cancellation of the sum) the status is
+ *   VC_DISP_CONVERGED  f'' < 0 and f'^2 / -f'' <= tol
+ *   VC_DISP_ROUNDING   |f'| <= noise
+ *   VC_DISP_AT_UPPER   f'(VC_DISP_RHO_MAX) > -noise: no detectable overdispersion (decided first)
+ *   VC_DISP_AT_LOWER   f'(VC_DISP_RHO_MIN) < noise (decided second)
+ *   VC_DISP_MAX_ITER   max_iter steps of the bracketed Newton iteration were taken (Newton step where f'' < 0 and it stays strictly
+ *                      inside the sign bracket of f', else its midpoint)
+ *   VC_DISP_EVALUATED  max_iter == 0
+ *   VC_DISP_NO_DATA    a coefficient of the gene is not finite: every output NaN
+ * Outputs per gene, at the last point: rho_dev double[Ng]; r_dev float[Ng] = e^rho rounded (what vc_gene_glm and vc_phase_mle read;
+ * evaluate-only: r_start itself); info_dev double[Ng] = -f'' (NaN at a bound); loglik_dev double[Ng] = L without the prior term;
+ * score_dev double[Ng] = f'; iterations_dev, status_dev int32[Ng].  A gene's status touches no other gene's outputs; every path is
+ * bounded.  VC_ERR_ARG (as vc_gene_glm's, max_iter < 0, one prior pointer without the other, max_iter == 0 without r_start_dev): all
+ * decided before anything is launched.  Errors: vc_last_error(NULL). */
+#define VC_DISP_RHO_MIN (-6.907755278982137)  /* ln 1e-3 */
+#define VC_DISP_RHO_MAX 13.815510557964274    /* ln 1e6 */
+#define VC_DISP_CONVERGED 0
+#define VC_DISP_ROUNDING 1
+#define VC_DISP_AT_UPPER 2
+#define VC_DISP_AT_LOWER 3
+#define VC_DISP_MAX_ITER 4
+#define VC_DISP_EVALUATED 5
+#define VC_DISP_NO_DATA 6
+int vc_gene_dispersion(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* basis_dev, int K,
+                       const float* logm_dev, const double* nu_dev, const float* r_start_dev, const double* prior_alpha_dev,
+                       const double* prior_beta_dev, double tol, int max_iter, double* rho_dev, float* r_dev, double* info_dev,
+                       double* loglik_dev, double* score_dev, int32_t* iterations_dev, int32_t* status_dev, void* hip_stream);
 
 /* --- PCA phase prior (Phases.from_pca_heuristic, phases.py:307-382): staging and the power iteration's pass ------------------
  * Stand-alone (no engine); the iteration itself (QR, Rayleigh-Ritz on 8 x 8 matrices, float64) is the caller's:

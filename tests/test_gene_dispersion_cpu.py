@@ -1,0 +1,336 @@
+"""CPU: the checker of the per-gene dispersion estimate (tests/gene_dispersion_checker.py) against finite differences, scipy.special and
+the simulation's truth; the bars it sets for tests/test_hip_gene_dispersion.py; the public face of `gene_dispersion` and
+`gene_harmonics(dispersion="mle")` (refusals before any device work, container plumbing); the C ABI declaration, its binding and its
+refusals; the kernel's code object."""
+import ctypes as C
+import inspect
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pandas as pd
+import pytest
+import torch
+
+from tests import gene_dispersion_checker as D
+from tests import gene_glm_checker as G
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _gene(name="shape_257_5_1", g=0):
+    p = D.cases()[name]
+    k, B, logm = D.gene_inputs(p, g)
+    return k, p["nu"][g] @ B + logm, p
+
+
+@pytest.mark.parametrize("r", [0.05, 2.0, 1e3, 1e5])
+def test_score_and_curvature_are_the_derivatives_of_L(r):
+    """f' against the central difference of L, f'' against the central difference of f', in rho = ln r; with and without the prior.
+    Where scipy.special's differences are good (r <= 1e3) the formulas as they stand agree with the reference."""
+    for prior in (None, (2.0, 1.5)):
+        k, eta, _ = _gene()
+        rho, h = math.log(r), 1e-4
+        pa, pb = D._prior(prior)
+        f = lambda x: D.point64(math.exp(x), k, eta, prior)["L"] - pa * x - pb * math.exp(-x)      # noqa: E731
+        p, up, dn = (D.point64(math.exp(x), k, eta, prior) for x in (rho, rho + h, rho - h))
+        fd = (f(rho + h) - f(rho - h)) / (2 * h)                      # truncation of the order h^2, rounding eps64 |L| / h
+        assert abs(fd - p["fp"]) <= 1e-6 * max(abs(p["fp"]), abs(p["fpp"])) + 4 * D.EPS64 * abs(p["L"]) / h
+        assert abs((up["fp"] - dn["fp"]) / (2 * h) - p["fpp"]) <= 1e-6 * abs(p["fpp"])
+        if r <= 1e3:
+            L, fp, fpp = D.point_scipy(r, k, eta, prior)
+            assert abs(L - p["L"]) <= 1e-12 * p["abs"] and abs(fp - p["fp"]) <= 1e-9 * abs(p["fp"]) and abs(fpp - p["fpp"]) <= 1e-9 * abs(p["fpp"])
+
+
+def test_scipy_differences_lose_the_score_near_the_poisson_limit():
+    """Why the reference does not take psi(k + r) - psi(r) from scipy.special: at r = 1e6 the score is a 1e-7 of its parts, and the
+    differences of digamma are off by more than the kernel's whole noise allowance."""
+    k, eta, _ = _gene()
+    p = D.point64(1e6, k, eta)
+    assert abs(D.point_scipy(1e6, k, eta)[1] - p["fp"]) > p["noise"]
+    assert abs(p["fp"]) < 1e-6 * p["noise"] / (64 * D.EPS64)
+
+
+@pytest.mark.parametrize("name", ["shape_257_5_1", "large_u16", "large_f32", "bound_lower"])
+def test_histogram_identity(name):
+    """sum_c g(k_c + r) - g(r) = sum_{j < T} N_{>j} g'(r + j) + the Stirling remainders of the counts >= T, for lgamma, psi and psi',
+    against the direct sums in extended precision."""
+    k, _, _ = _gene(name)
+    assert k.max() >= D.T or not name.startswith("large")
+    for r in (1e-3, 0.05, 2.0, 1e3, 1e6):
+        direct = [float(t.sum()) for t in D.gamma_sums(r, k)]
+        got = D.histogram_sums(r, k)
+        assert np.allclose(got, direct, rtol=1e-13, atol=0), (r, got, direct)
+
+
+def test_stirling_differences_at_the_smallest_argument():
+    from scipy.special import gammaln
+    dk = np.array([0.0, 1.0, 7.0, 3000.0, 69000.0])
+    for r in (1e-3, 5.0, 1e6):
+        x0 = r + D.T
+        want = D.gamma_sums(x0, dk)
+        got = D.stirling_differences(x0, dk)
+        for a, b in zip(got, want):
+            assert np.allclose(a, np.asarray(b, dtype=np.float64), rtol=2e-14, atol=0)
+        assert got[0][0] == 0 and got[1][0] == 0 and got[2][0] == 0
+        assert np.allclose(got[0], gammaln(x0 + dk) - gammaln(x0), rtol=1e-9)
+
+
+def test_every_reference_fit_of_the_gpu_cases_has_a_definite_status():
+    for name in D.cases():
+        for (f64, f32) in D.solved(name):
+            assert f64["status"] in (D.CONVERGED, D.AT_UPPER, D.AT_LOWER), name
+            if f64["status"] == D.CONVERGED:
+                assert f32["status"] in D.INTERIOR and f64["info"] > 0 and f32["iterations"] <= 10, name
+            else:
+                assert f32["status"] == f64["status"], name
+    assert D.solved("bound_binomial_prior")[0][0]["status"] == D.CONVERGED
+    assert D.solved("shape_1_1_0")[0][0]["status"] == D.AT_UPPER                       # one cell at its own mean: nothing to see
+    assert abs(D.solved("large_u16")[0][0]["rho"] + 2.788) < 1e-3
+
+
+def test_bound_cases_are_far_from_their_noise():
+    """|f'| at the bound is at least 100 x the noise rule, so that the status cannot flip on rounding."""
+    for name, want in D.BOUND_CASES.items():
+        f64, f32 = D.solved(name)[0]
+        assert f64["status"] == want == f32["status"]
+        assert abs(f64["fp"]) >= 100 * f64["noise"] and abs(f32["fp"]) >= 100 * f32["noise"], name
+        assert np.isnan(f64["info"]) and np.isnan(f32["info"])
+
+
+def test_bars_come_from_the_restatement():
+    w, bars = D.worst(), D.bars()
+    print("the restatement's worst:", {k: float(f"{v:.4g}") for k, v in w.items()})
+    print("bars:", {k: float(f"{v:.4g}") for k, v in bars.items()})
+    for key, v in bars.items():
+        assert np.isfinite(v) and v > 0 and v == D.SAFETY * w[key] + (math.sqrt(D.TOL) if key == "rho" else 0.0)
+    assert bars["rho"] < 1e-3 and bars["std"] < 1e-4 and bars["stat_r"] < 1e-3
+    # the float32 mu alone (both iterations run to the end) moves rho by far less than the stopping rule allows
+    k, eta, p = _gene()
+    far = D.restate(k, *D.gene_inputs(p, 0)[1:], p["nu"][0], tol=0.0)
+    assert far["status"] == D.ROUNDING and abs(far["rho"] - D.solved("shape_257_5_1")[0][0]["rho"]) * math.sqrt(far["info"]) < 1e-5
+
+
+def test_evaluate_only_restatement_is_within_its_own_noise_rule():
+    """The restatement's score differs from the reference by about the noise rule's size at most (the rule is what one float32 rounding
+    of mu does to f'), also at r = 1e6 where the sum is 1e-7 of its parts."""
+    for (r, g), (ref, f32) in D.evaluated().items():
+        assert f32["status"] == D.EVALUATED
+        d = D.point_distances(f32["L"], f32["fp"], ref)
+        assert d["score"] <= 2.0 and d["loglik"] <= 2.0, (r, g, d)
+        assert abs(f32["noise"] / ref["noise"] - 1) < 1e-3
+
+
+def test_reference_recovers_the_simulation():
+    """The joint reference fit of the model-simulated problem: every overdispersed gene within 4 standard errors of its r, the Poisson
+    gene at the upper bound, a handful of rounds."""
+    p = D.joint_problem()
+    for g, (f64, f32) in enumerate(D.joint_solved()):
+        if g == D.POISSON_GENE:
+            assert f64["disp"]["status"] == D.AT_UPPER == f32["status"]
+            continue
+        assert f64["disp"]["status"] == D.CONVERGED and f32["status"] in D.INTERIOR
+        assert abs(f64["rho"] - math.log(p["r_true"][g])) <= 4 * f64["disp"]["std"], g
+        assert f64["rounds"] <= 8 and f32["rounds"] <= 5
+        z = (f64["nu"] - p["nu_true"][g]) / f64["glm"]["std"]
+        assert np.abs(z).max() <= 5.0
+
+
+def test_overdispersion_p_is_the_boundary_mixture():
+    from scipy.stats import chi2
+    from velocycle_amd import _lib
+    from dataclasses import fields
+    from velocycle_amd.gene_harmonics import MLE_FIELDS, GeneHarmonicFit, overdispersion_p_value
+    lr = np.array([0.0, 0.3, 2.0, 17.5, 140.0, -1e-9, np.nan])
+    p = overdispersion_p_value(lr)
+    assert np.allclose(p[:5], 0.5 * chi2.sf(lr[:5], 1), rtol=1e-12, atol=0) and p[5] == 0.5 and np.isnan(p[6])
+    assert np.allclose([D.overdispersion_p(v) for v in lr[:5]], 0.5 * chi2.sf(lr[:5], 1), rtol=1e-12, atol=0)
+    st = np.array([0, 1, _lib.VC_DISP_AT_UPPER, 0, 0, _lib.VC_DISP_AT_UPPER, 0])
+    assert (overdispersion_p_value(lr, st)[[2, 5]] == 1).all() and (overdispersion_p_value(lr, st)[[0, 1, 3]] == p[[0, 1, 3]]).all()
+    fit = GeneHarmonicFit(means=np.zeros((3, 2)), stds=np.ones((3, 2)), cov=np.zeros((2, 3, 3)), loglik=np.array([1.0, 5.0]),
+                          loglik_null=np.zeros(2), decrement=np.zeros(2), iterations=np.zeros(2, np.int32), status=np.zeros(2, np.int32))
+    assert fit.dispersion is None and fit.log_r_std is None and fit.dispersion_status is None and fit.rounds is None
+    assert fit.loglik_poisson is None and fit.overdispersion_p is None and fit.overdispersion_lr is None
+    fit.loglik_poisson = np.array([0.5, 1.0])
+    assert (fit.overdispersion_lr == [1.0, 8.0]).all()
+    # trailing arguments of the constructor, in this order; code that walks dataclasses.fields() meets the eight arrays only
+    six = [np.full(2, float(i)) for i in range(6)]
+    full = GeneHarmonicFit(*[getattr(fit, f.name) for f in fields(fit)], *six)
+    assert MLE_FIELDS == ("dispersion", "log_r_std", "dispersion_status", "rounds", "loglik_poisson", "overdispersion_p")
+    assert all(getattr(full, name) is six[i] for i, name in enumerate(MLE_FIELDS))
+    assert [f.name for f in fields(full)] == ["means", "stds", "cov", "loglik", "loglik_null", "decrement", "iterations", "status"]
+
+
+def test_signatures():
+    from velocycle_amd.gene_harmonics import MLE_OPTIONS, GeneDispersionFit, gene_dispersion, gene_harmonics
+    sig = inspect.signature(gene_dispersion)
+    assert [(n, p.default) for n, p in sig.parameters.items() if p.kind == p.POSITIONAL_OR_KEYWORD] == \
+        [("counts", inspect.Parameter.empty), ("directions", inspect.Parameter.empty), ("n_scounts", inspect.Parameter.empty),
+         ("means", inspect.Parameter.empty), ("a", 1)]
+    assert {n: p.default for n, p in sig.parameters.items() if p.kind == p.KEYWORD_ONLY} == \
+        {"start": None, "prior": None, "tol": 1e-10, "max_iter": 50, "evaluate_only": False, "device": None, "chunk_genes": None,
+         "storage": "auto"}
+    assert MLE_OPTIONS == {"dispersion_start": 0.3, "dispersion_prior": None, "rho_tol": 1e-6, "max_rounds": 10}
+    assert any(p.kind == p.VAR_KEYWORD for p in inspect.signature(gene_harmonics).parameters.values())
+    assert [f for f in GeneDispersionFit.__dataclass_fields__] == ["dispersion", "log_r", "log_r_std", "loglik", "score", "iterations", "status"]
+
+
+@pytest.fixture
+def no_device(monkeypatch):
+    from velocycle_amd import _lib
+
+    def reached(*a, **k):
+        raise AssertionError("the device path was reached")
+    monkeypatch.setattr(_lib, "load", reached)
+    monkeypatch.setattr(torch.cuda, "is_available", reached)
+
+
+def test_refusals_fire_before_the_device(no_device):
+    from velocycle_amd.gene_harmonics import gene_dispersion, gene_harmonics
+    S = (np.arange(24, dtype=np.float32).reshape(6, 4) % 5) + 1
+    xy, n = G.directions(np.linspace(0.1, 6.0, 6)), S.sum(1)
+    nb = dict(noisemodel="NegativeBinomial", dispersion="mle")
+    with pytest.raises(ValueError, match="Poisson model has no dispersion"):
+        gene_harmonics(S, xy, n, dispersion="mle")
+    with pytest.raises(ValueError, match="'mle'"):
+        gene_harmonics(S, xy, n, noisemodel="NegativeBinomial", dispersion="fit")
+    with pytest.raises(NotImplementedError):
+        gene_harmonics(S, xy, n, noisemodel="Lognormal", dispersion="mle")
+    with pytest.raises(TypeError, match="rho_tolerance"):
+        gene_harmonics(S, xy, n, rho_tolerance=1e-3, **nb)
+    with pytest.raises(ValueError, match="rho_tol"):
+        gene_harmonics(S, xy, n, rho_tol=-1.0, **nb)
+    for bad in (0, 2.5):
+        with pytest.raises(ValueError, match="max_rounds"):
+            gene_harmonics(S, xy, n, max_rounds=bad, **nb)
+    with pytest.raises(ValueError, match="dispersion"):
+        gene_harmonics(S, xy, n, dispersion_start=0.0, **nb)
+    with pytest.raises(ValueError, match="dispersion"):
+        gene_harmonics(S, xy, n, dispersion_start=np.full(3, 0.3), **nb)
+    with pytest.raises(ValueError, match="alpha, beta"):
+        gene_harmonics(S, xy, n, dispersion_prior=(1.0, 2.0, 3.0), **nb)
+    with pytest.raises(ValueError, match="one value per gene"):
+        gene_harmonics(S, xy, n, dispersion_prior=(np.ones(3), 1.0), **nb)
+    with pytest.raises(ValueError, match="directions"):
+        gene_harmonics(S, xy[:, :5], n, **nb)
+    means = np.zeros((3, 4))
+    with pytest.raises(ValueError, match="means"):
+        gene_dispersion(S, xy, n, np.zeros((2, 4)))
+    with pytest.raises(ValueError, match="means"):
+        gene_dispersion(S, xy, n, np.zeros(4))
+    with pytest.raises(ValueError, match="genes"):
+        gene_dispersion(S, xy, n, np.zeros((3, 5)))
+    with pytest.raises(ValueError, match="evaluate_only needs start"):
+        gene_dispersion(S, xy, n, means, evaluate_only=True)
+    with pytest.raises(ValueError, match="max_iter"):
+        gene_dispersion(S, xy, n, means, max_iter=0)
+    with pytest.raises(ValueError, match="tol"):
+        gene_dispersion(S, xy, n, means, tol=-1.0)
+    with pytest.raises(ValueError, match="dispersion"):
+        gene_dispersion(S, xy, n, means, start=-0.3)
+    with pytest.raises(ValueError, match="alpha, beta"):
+        gene_dispersion(S, xy, n, means, prior=(1.0,))
+    with pytest.raises(ValueError, match="n_scounts"):
+        gene_dispersion(S, xy, n[:5], means)
+    with pytest.raises(ValueError, match="storage"):
+        gene_dispersion(S, xy, n, means, storage="u8")
+    with pytest.raises(ValueError, match="chunk_genes"):
+        gene_dispersion(S, xy, n, means, chunk_genes=0)
+    Z = S.copy()
+    Z[:, 1] = 0
+    with pytest.raises(ValueError, match=r"1 of 4 genes have no count"):
+        gene_dispersion(Z, xy, n, means)
+
+
+def test_container_plumbing(monkeypatch):
+    from velocycle_amd import gene_harmonics as GH
+    from velocycle_amd.anndata_lite import AnnDataLite
+    from velocycle_amd.containers import Cycle, Phases
+    S = (np.arange(24, dtype=np.float32).reshape(6, 4) % 5) + 1
+    ad = AnnDataLite(S, S, obs=pd.DataFrame({"n_scounts": S.sum(1)}, index=[f"c{i}" for i in range(6)]))
+    ph = Phases.from_array(G.directions(np.linspace(0.1, 6.0, 6)) * 3.0, cell_names=list(ad.obs.index))
+    seen = {}
+
+    def fake(counts, directions, n_scounts, harmonics=1, a=1, noisemodel="Poisson", dispersion=0.3, **kw):
+        seen.update(dispersion=dispersion, noisemodel=noisemodel, kw=kw)
+        K, Ng = 2 * harmonics + 1, counts.shape[1]
+        fit = GH.GeneHarmonicFit(means=np.zeros((K, Ng)), stds=np.ones((K, Ng)), cov=np.zeros((Ng, K, K)), loglik=np.ones(Ng),
+                                 loglik_null=np.zeros(Ng), decrement=np.zeros(Ng), iterations=np.zeros(Ng, np.int32),
+                                 status=np.zeros(Ng, np.int32))
+        if isinstance(dispersion, str):
+            fit.dispersion = np.linspace(0.1, 0.4, Ng)
+        return fit
+    monkeypatch.setattr(GH, "gene_harmonics", fake)
+    cyc, fit = Cycle.from_phases_mle(ph, ad, 1, 1, "NegativeBinomial", "mle", return_fit=True, dispersion_start=0.5, max_rounds=4)
+    assert seen["dispersion"] == "mle" and seen["kw"]["dispersion_start"] == 0.5 and seen["kw"]["max_rounds"] == 4
+    assert cyc.disp_pyro is fit.dispersion and (cyc.disp_pyro == np.linspace(0.1, 0.4, 4)).all()
+    plain = Cycle.from_phases_mle(ph, ad, 1, 1, "NegativeBinomial", 0.3)
+    assert plain.disp_pyro is None and seen["dispersion"] == 0.3
+
+
+def test_header_declares_and_lib_binds_vc_gene_dispersion():
+    from velocycle_amd import _lib
+    from velocycle_amd.gene_harmonics import DISPERSION_STATUS
+    hdr = open(os.path.join(ROOT, "include", "velocycle_hip.h")).read()
+    assert " *   vc_gene_dispersion " in hdr and "#define VC_ABI_VERSION 2" in hdr
+    names = ["CONVERGED", "ROUNDING", "AT_UPPER", "AT_LOWER", "MAX_ITER", "EVALUATED", "NO_DATA"]
+    for i, name in enumerate(names):
+        assert f"#define VC_DISP_{name} {i}" in hdr and getattr(_lib, f"VC_DISP_{name}") == i == getattr(D, name)
+        assert DISPERSION_STATUS[i] == name
+    lo = float(re.search(r"#define VC_DISP_RHO_MIN \((-[0-9.]+)\)", hdr).group(1))
+    hi = float(re.search(r"#define VC_DISP_RHO_MAX ([0-9.]+)", hdr).group(1))
+    assert lo == D.RHO_MIN == _lib.VC_DISP_RHO_MIN == math.log(1e-3) and hi == D.RHO_MAX == _lib.VC_DISP_RHO_MAX == math.log(1e6)
+    decl = re.search(r"\bint vc_gene_dispersion\(([^;]*)\);", hdr).group(1)
+    assert len(_lib.EXPORTS["vc_gene_dispersion"][1]) == len(decl.split(",")) == 22 and decl.rstrip().endswith("void* hip_stream")
+    src = open(os.path.join(ROOT, "velocycle_amd", "csrc", "vc_gene_dispersion.hip")).read()
+    assert f"DSP_T = {D.T};" in src and "#pragma clang fp contract(off)" in src and "atomicAdd(&ngt[" in src
+    assert len(re.findall(r"atomic", src.split("namespace {")[1])) == 1           # the one integer LDS atomic of the histogram; no float atomics
+
+
+def disp_args(**k):
+    """Arguments of vc_gene_dispersion with pointers that are never dereferenced: every call made with them is refused before the launch."""
+    one = C.c_void_p(64)
+    return [k.get("counts", one), k.get("kind", 0), k.get("Ng", 4), k.get("Nc", 4), k.get("stride", 4), k.get("basis", one), k.get("K", 3),
+            k.get("logm", one), k.get("nu", one), k.get("r_start", None), k.get("pa", None), k.get("pb", None), k.get("tol", 1e-10),
+            k.get("max_iter", 50), k.get("rho", one), k.get("r", one), k.get("info", one), k.get("ll", one), k.get("score", one),
+            k.get("it", one), k.get("st", one), None]
+
+
+REFUSALS = [(dict(K=K), b"K must be") for K in (0, 2, 4, 9)] + \
+    [({name: None}, b"null") for name in ("counts", "basis", "logm", "nu", "rho", "r", "info", "ll", "score", "it", "st")] + \
+    [(dict(Nc=0), b"Nc"), (dict(Ng=0), b"Ng"), (dict(Nc=1 << 31, stride=1 << 31), b"2^31"), (dict(stride=3), b"gene_stride"),
+     (dict(max_iter=-1), b"max_iter"), (dict(max_iter=0), b"r_start_dev"), (dict(tol=-1e-3), b"tol"), (dict(tol=float("nan")), b"tol"),
+     (dict(pa=C.c_void_p(64)), b"prior"), (dict(pb=C.c_void_p(64)), b"prior"), (dict(kind=7), b"count_kind")]
+
+
+def test_entry_point_validates_without_a_device():
+    from velocycle_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    lib = _lib.load()
+    for kw, msg in REFUSALS:
+        assert lib.vc_gene_dispersion(*disp_args(**kw)) == _lib.VC_ERR_ARG and msg in lib.vc_last_error(None), kw
+    src = open(os.path.join(ROOT, "velocycle_amd", "csrc", "vc_gene_dispersion.hip")).read()
+    body = src[src.index('extern "C" int vc_gene_dispersion'):]
+    assert body.rindex("dsp_fail(") < body.index("hipLaunchKernelGGL")                  # every refusal comes before the launch
+
+
+def test_the_kernel_has_no_scratch(tmp_path):
+    """Every instantiation of vc_gene_dispersion_kernel reports .private_segment_fixed_size 0 in the metadata of the assembly emitted
+    for gfx950 (hipcc -S --cuda-device-only), and an LDS footprint that leaves eight workgroups to a compute unit."""
+    hipcc = "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    src = os.path.join(ROOT, "velocycle_amd", "csrc", "vc_gene_dispersion.hip")
+    out = str(tmp_path / "disp.s")
+    subprocess.run([hipcc, "-falign-loops=64", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", src, "-o", out],
+                   check=True, capture_output=True)
+    txt = open(out).read()
+    found = re.findall(r"\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S*vc_gene_dispersion_kernel\S*)\n(?:.*\n)*?"
+                       r"\s+\.private_segment_fixed_size:\s+(\d+)", txt)
+    assert len(found) == 8, len(found)                     # H 0..3 x {u16, f32}
+    assert all(int(p) == 0 for _, _, p in found), found
+    assert all(8 * int(lds) <= 160 * 1024 for lds, _, _ in found), found

@@ -139,7 +139,9 @@ class Cycle(_HarmonicTable):
         (mu = exp(nu . zeta(phi)) n_scounts^a, Poisson or NegativeBinomial; reference phases.py:487-507) solved for the gene harmonics,
         one log-link regression on the Fourier design per gene, by the HIP kernel behind `velocycle_amd.gene_harmonics.gene_harmonics`.
         means = the maximum-likelihood coefficients (with `prior`, a Cycle over the same genes and harmonics: the posterior modes under
-        its Gaussians), stds = sqrt of the diagonal of the inverse observed Hessian.  `dispersion` may be one value per gene; the layer may
+        its Gaussians), stds = sqrt of the diagonal of the inverse observed Hessian.  `dispersion` may be one value per gene, or "mle"
+        (NegativeBinomial): the dispersion of every gene is then estimated with its harmonics and stored as `disp_pyro`, which
+        `Phases.from_cycle_mle(cycle, data, noisemodel="NegativeBinomial", dispersion=cycle.disp_pyro)` consumes; the layer may
         be dense or sparse.  Keyword-only: `layer`, `prior`, `return_fit=True` returns (Cycle, GeneHarmonicFit) -- the fit holds the
         log-likelihoods, the likelihood-ratio statistic for periodicity and its p-value, and how every gene's iteration ended; anything
         else goes to the worker (tol, max_iter, device, chunk_genes, storage)."""
@@ -170,6 +172,8 @@ class Cycle(_HarmonicTable):
                              harmonics=harmonics, a=a, noisemodel=noisemodel, dispersion=dispersion, prior_means=prior_means,
                              prior_stds=prior_stds, **worker_kw)
         out = cls.from_array(fit.means, fit.stds, gene_names=data.var.index)
+        if fit.dispersion is not None:                                   # dispersion="mle": the field the reference keeps shape_inv in
+            out.set_disp_pyro(fit.dispersion)
         return (out, fit) if return_fit else out
 
 
