@@ -41,6 +41,9 @@
  *   vc_gene_dispersion          no counterpart (the reference learns shape_inv only inside the SVI, velocity_inference_model.py:383):
  *                               the maximum-likelihood (or Gamma-prior mode) negative-binomial dispersion per gene with the means of
  *                               vc_gene_glm known; stand-alone, no engine
+ *   vc_gene_kinetics            no counterpart (the reference learns logγg, logβg and νω only inside the SVI): the unspliced half of
+ *                               velocity_inference_model.py:360-386 solved per gene for (log gamma, log beta) with the cycle, the
+ *                               phases and the angular speed known, and the score and profile information of νω; stand-alone
  *   vc_pca_stage, vc_pca_apply  Phases.from_pca_heuristic (phases.py:307-382): np.log(layer + small_count) and the one large
  *                               operation of a block power iteration that replaces sklearn's PCA(n_components).fit_transform
  *                               (:343-349); stand-alone, no engine
@@ -593,6 +596,66 @@ int vc_gene_dispersion(const void* counts_dev, int count_kind, int64_t Ng, int64
                        const float* logm_dev, const double* nu_dev, const float* r_start_dev, const double* prior_alpha_dev,
                        const double* prior_beta_dev, double tol, int max_iter, double* rho_dev, float* r_dev, double* info_dev,
                        double* loglik_dev, double* score_dev, int32_t* iterations_dev, int32_t* status_dev, void* hip_stream);
+
+/* --- per-gene kinetics of the velocity model given the cycle, the phases and the angular speed (stand-alone: no engine handle) ---
+ * The unspliced half of velocity_inference_model.py:360-386 (with_delta_nu=False) solved for x = log gamma_g, y = log beta_g:
+ *   etaS = nu_g . basis[:, c] + logm[c]                                        (vc_gene_glm's eta)
+ *   d    = sum_h h (nu_sin_h cos h phi - nu_cos_h sin h phi)                   (from the same basis rows)
+ *   om   = sum_i nuw[i] w[i][c],   z = om d + e^x,   a = [z > 0],   zp = a z + 1e-5
+ *   etaU = etaS - y + ln zp,   mu = e^(etaS - y) zp
+ *   L(x, y) = Poisson  sum_c k etaU - mu     NB  sum_c k etaU - (k + r) ln(r + mu) + Nc r ln r          (vc_gene_glm's convention)
+ *   f(x, y) = L - (x - mu_gamma)^2 / 2 sd_gamma^2 - (y - mu_beta)^2 / 2 sd_beta^2                       (the model's Normal priors)
+ * One workgroup per gene, one launch, no workspace, no allocation, no synchronisation; asynchronous on hip_stream.  Every pointer is
+ * DEVICE memory.  counts_dev (the UNSPLICED counts), count_kind, Ng, Nc, gene_stride, basis_dev, logm_dev: as for vc_gene_glm, with
+ * K = 2 H + 1 in {3, 5} (H = 0 has no velocity; H = 3 is not instantiated); Nc <= 2^31 - 1.
+ *   nu_dev          double[Ng][K]: the cycle's coefficients (vc_gene_glm's nu_dev)
+ *   w_dev, NW, nuw_dev   float[NW][Nc] and double[NW], NW in 0..3: the rows of the angular speed's design (condition indicator times
+ *                   zeta_omega(phi_c)) and its coefficients, shared by the genes; NW = 0 (both NULL): om = 0
+ *   noise, r_dev    as for vc_gene_glm
+ *   prior_dev       double[Ng][4]: mu_gamma, sd_gamma, mu_beta, sd_beta (the model's defaults: 0, 0.5, 2, 3)
+ *   start_dev       double[Ng][2] or NULL: where the iteration starts; NULL: x = mu_gamma, y = ln(sum_c e^etaS zp / sum_c k)
+ *   tol, max_iter   stop at the decrement G' A^-1 G <= tol (>= 0) after at most max_iter steps; max_iter == 0 evaluates at start_dev only
+ * etaS, d, om, z and etaS - y are float64 (the set of clamped cells z <= 0 is that of a float64 evaluation of the float32 tables);
+ * e^(etaS - y) is formed as vc_gene_glm forms mu (one float32 exp2) and multiplied by zp in float32; the residual, the weights, the
+ * NB logarithm and ln zp are float32; every sum is float64 in a fixed order, the 2 x 2 algebra float64: identical bits under
+ * repetition, uint16 or float32 storage, and any cutting of the genes into calls.  With g = (p, -1), p = a e^x / zp, the gradient is
+ * G = sum_c res g - prior terms (res = k - mu | (k - mu) r / (r + mu)), and a step is A^-1 G with A the observed matrix
+ * sum_c wo g g' - [sum_c res p (1 - p)]_xx + diag(1 / sd^2) (wo = mu | mu r (k + r) / (r + mu)^2) where that is positive definite,
+ * else the Fisher matrix sum_c w g g' + diag(1 / sd^2) (w = mu | mu r / (r + mu)); (x, y) stays in [-30, 30]^2.  Status per gene:
+ *   VC_KIN_CONVERGED  dec <= tol
+ *   VC_KIN_ROUNDING   vc_gene_glm's rule on the two gradients: |G_x| <= 4 eps32 sqrt(sum_c (wo^2 + res^2) p^2) and
+ *                     |G_y| <= 4 eps32 sqrt(sum_c wo^2 + res^2)
+ *   VC_KIN_MAX_ITER   max_iter steps were taken, the gene used up its 30 step halvings (a step is halved while f drops by more than
+ *                     its own float32 rounding, 8 eps32 sum |terms|), or the decrement is not finite
+ *   VC_KIN_UNBOUNDED  a step would take x or y out of [-30, 30] (a full step of the observed matrix that would is first replaced by
+ *                     the Fisher matrix's: a barely positive definite observed matrix is no sign of an unbounded fit); the last point
+ *                     inside is kept
+ *   VC_KIN_NO_DATA    a coefficient (nu, nuw), a prior or r is not finite (sd, r: or not > 0), a start is not finite, or the gene has
+ *                     no count: every output NaN (iterations, n_clamped 0)
+ *   VC_KIN_EVALUATED  max_iter == 0
+ * Outputs per gene, at the last accepted point:
+ *   xy_dev          double[Ng][2]: x, y
+ *   cov_dev         double[Ng][3]: A^-1 of the matrix A the decrement there was formed with, packed (xx, yx, yy)
+ *   loglik_dev      double[Ng]: L, without the prior term;  dec_dev double[Ng];  iterations_dev int32[Ng]: steps taken
+ *   status_dev      int32[Ng];  n_clamped_dev int32[Ng]: the number of cells with z <= 0
+ *   score_w_dev     double[Ng][NW]: sum_c res q w[i][c], q = a d / zp -- d f / d nuw_i at the point (NW > 0)
+ *   info_w_dev      double[Ng][NW (NW + 1) / 2]: the profile information I_ww - I_wt (I_tt + diag(1 / sd^2))^-1 I_tw of nuw, with
+ *                   I = sum_c w g g' over g = (q w[.][c], p, -1), lower triangle packed row by row (NW > 0; one further pass)
+ * A gene's status touches no other gene's outputs; every path is bounded.  VC_ERR_ARG (NULL input or output, K not in {3, 5}, NW
+ * outside 0..3, NW > 0 without w_dev, nuw_dev, score_w_dev or info_w_dev, NB without r_dev, Nc < 1, Ng < 1, gene_stride < Nc,
+ * max_iter < 0, max_iter == 0 without start_dev, tol < 0), VC_ERR_UNSUPPORTED (Lognormal): all decided before anything is launched.
+ * Errors: vc_last_error(NULL). */
+#define VC_KIN_CONVERGED 0
+#define VC_KIN_ROUNDING 1
+#define VC_KIN_MAX_ITER 2
+#define VC_KIN_UNBOUNDED 3
+#define VC_KIN_NO_DATA 4
+#define VC_KIN_EVALUATED 5
+int vc_gene_kinetics(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* basis_dev, int K,
+                     const float* logm_dev, const double* nu_dev, const float* w_dev, int NW, const double* nuw_dev, int noise,
+                     const float* r_dev, const double* prior_dev, const double* start_dev, double tol, int max_iter, double* xy_dev,
+                     double* cov_dev, double* loglik_dev, double* dec_dev, int32_t* iterations_dev, int32_t* status_dev,
+                     int32_t* n_clamped_dev, double* score_w_dev, double* info_w_dev, void* hip_stream);
 
 /* --- PCA phase prior (Phases.from_pca_heuristic, phases.py:307-382): staging and the power iteration's pass ------------------
  * Stand-alone (no engine); the iteration itself (QR, Rayleigh-Ritz on 8 x 8 matrices, float64) is the caller's:

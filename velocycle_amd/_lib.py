@@ -24,7 +24,8 @@ NOISE = {"NegativeBinomial": 0, "Poisson": 1, "Lognormal": 2}
 VC_COUNTS_F32, VC_COUNTS_U16 = 0, 1
 VC_GLM_CONVERGED, VC_GLM_ROUNDING, VC_GLM_UNBOUNDED, VC_GLM_SINGULAR, VC_GLM_MAX_ITER = 0, 1, 2, 3, 4
 VC_DISP_CONVERGED, VC_DISP_ROUNDING, VC_DISP_AT_UPPER, VC_DISP_AT_LOWER, VC_DISP_MAX_ITER, VC_DISP_EVALUATED, VC_DISP_NO_DATA = range(7)
-VC_DISP_RHO_MIN, VC_DISP_RHO_MAX = -6.907755278982137, 13.815510557964274           # ln 1e-3, ln 1e6
+VC_KIN_CONVERGED, VC_KIN_ROUNDING, VC_KIN_MAX_ITER, VC_KIN_UNBOUNDED, VC_KIN_NO_DATA, VC_KIN_EVALUATED = range(6)
+VC_DISP_RHO_MIN, VC_DISP_RHO_MAX =-6.907755278982137, 13.815510557964274           # ln 1e-3, ln 1e6
 
 # sample sites, parameters and eps blocks, named as in the reference
 SITES = ["ϕxy", "ν", "Δν", "shape_inv", "logγg", "logβg", "νω", "rho_real"]
@@ -141,6 +142,10 @@ EXPORTS = {
     "vc_gene_dispersion": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vc_gene_kinetics": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "vc_pca_stage": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p]),
     "vc_pca_apply_workspace": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),

@@ -1,0 +1,389 @@
+"""The velocity half of the model solved deterministically on the HIP kernel `vc_gene_kinetics`: per-gene kinetics (log gamma, log beta)
+at a given angular speed (`gene_kinetics`), and the MAP angular speed νω with the kinetics profiled out (`velocity_map`, the worker
+behind `AngularSpeed.from_kinetics_mle`).
+
+The model is the reference's velocity stage conditioned on ϕxy and ν (velocity_inference_model.py:360-386, with_delta_nu=False):
+
+    etaS = nu_g . zeta(phi_c) + a log n_c,   d = nu_g . d zeta / d phi (phi_c),   omega_c = sum_i νω_i W_i(c)
+    z = omega_c d + gamma_g,   mu_U = exp(etaS) (relu(z) + 1e-5) / beta_g,   U ~ Poisson(mu_U) | NegativeBinomial(mu_U, r)
+    log gamma_g ~ Normal(0, 0.5),   log beta_g ~ Normal(2, 3),   νω ~ the Normals of an `AngularSpeed`
+
+With omega fixed every gene is a two-parameter problem, which the kernel solves by a Newton iteration inside one workgroup; the
+derivative of the profiled objective F(νω) = sum_g max_(x, y) f_g with respect to νω is the kernel's score (envelope theorem), its
+curvature the kernel's profile information, so νω follows by a damped Newton iteration of a handful of kernel calls on the host.
+`relu` makes f_g non-concave where cells have z <= 0 (`n_clamped` counts them): the fit is the model's, kink included.
+
+Genes are independent: they are staged in chunks exactly as `gene_harmonics` stages them, and the result does not depend on the chunk
+size, the storage or the layer's format bit for bit.  Cells cannot be cut.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from .gene_harmonics import (_check_run_options, _constants, _open_device, _ptr, _row_sums, _stage, default_chunk_genes,
+                             fourier_basis_from_directions)
+from .phase_mle import NOISEMODELS, _is_sparse
+
+HARMONICS = (1, 2)                   # csrc/vc_gene_kinetics.hip
+MAX_NW = 3
+DEFAULT_PRIOR = (0.0, 0.5, 2.0, 3.0)  # mu_gamma, sd_gamma, mu_beta, sd_beta: the model's
+EPS32 = float(np.finfo(np.float32).eps)
+STATUS = {_lib.VC_KIN_CONVERGED: "CONVERGED", _lib.VC_KIN_ROUNDING: "ROUNDING", _lib.VC_KIN_MAX_ITER: "MAX_ITER",
+          _lib.VC_KIN_UNBOUNDED: "UNBOUNDED", _lib.VC_KIN_NO_DATA: "NO_DATA", _lib.VC_KIN_EVALUATED: "EVALUATED"}
+MAP_STATUS = ("CONVERGED", "STALLED", "MAX_ROUNDS", "GENE_FAILED")
+MAX_OUTER_HALVINGS = 10
+
+
+def _with_kinetics(cycle, log_gamma, log_beta):
+    out = cycle.copy()
+    out.set_log_gammas(np.array(log_gamma, dtype=np.float64))
+    out.set_log_betas(np.array(log_beta, dtype=np.float64))
+    return out
+
+
+@dataclass
+class GeneKineticsFit:
+    """Host float64 arrays.  log_gamma, log_beta: [Ng]; cov: [Ng, 2, 2], the inverse of the matrix the last decrement was formed with
+    (the observed Hessian of the penalised objective where it is positive definite, else the Fisher matrix; both with the prior
+    precisions); stds: [2, Ng] = sqrt of its diagonal; loglik: [Ng] the full log-likelihood of the unspliced counts at the point
+    (without the prior); decrement; iterations, status, n_clamped: int32 [Ng] (`STATUS` names the codes; n_clamped = cells with
+    z <= 0 at the point); score_w: [Ng, NW] and info_w: [Ng, NW, NW], the score and the profile information of the angular speed's
+    coefficients."""
+    log_gamma: np.ndarray
+    log_beta: np.ndarray
+    cov: np.ndarray
+    stds: np.ndarray
+    loglik: np.ndarray
+    decrement: np.ndarray
+    iterations: np.ndarray
+    status: np.ndarray
+    n_clamped: np.ndarray
+    score_w: np.ndarray
+    info_w: np.ndarray
+
+    def to_cycle(self, cycle):
+        """A copy of `cycle` with `log_gammas` and `log_betas` set."""
+        return _with_kinetics(cycle, self.log_gamma, self.log_beta)
+
+
+@dataclass
+class VelocityMapFit:
+    """nu_omega, stds: [2 Hω + 1, Nx] float64 in `AngularSpeed`'s row layout; cov: [NW, NW] = J^-1 over the coefficients in the order
+    condition-major (i = x (2 Hω + 1) + h); F: the profiled log-posterior (full log-likelihood, the genes' and νω's Gaussian penalties);
+    dec: the last outer decrement; rounds: outer steps taken; status: one of `MAP_STATUS`; n_excluded: genes left out after the first
+    round; included: bool [Ng]; kinetics: the final `GeneKineticsFit`."""
+    nu_omega: np.ndarray
+    stds: np.ndarray
+    cov: np.ndarray
+    F: float
+    dec: float
+    rounds: int
+    status: str
+    n_excluded: int
+    included: np.ndarray
+    kinetics: GeneKineticsFit
+
+    def to_cycle(self, cycle):
+        """A copy of `cycle` with `log_gammas` and `log_betas` set."""
+        return self.kinetics.to_cycle(cycle)
+
+
+def check_arguments(counts, directions, n_scounts, means, a=1, noisemodel="Poisson", dispersion=0.3, prior=DEFAULT_PRIOR, start=None,
+                    evaluate_only=False, tol=1e-10, max_iter=25):
+    """Every refusal that needs no device.  Returns (basis float64 [K, Nc], logm float64 [Nc], nu float64 [Ng, K], r float64 [Ng] or
+    None, prior float64 [Ng, 4], start float64 [Ng, 2] or None)."""
+    if noisemodel not in NOISEMODELS:
+        raise NotImplementedError("Not implemented yet, sorry")
+    nu = np.asarray(means, dtype=np.float64)
+    if nu.ndim != 2 or nu.shape[0] not in (3, 5):
+        raise ValueError(f"means must be [2 harmonics + 1, genes] with 1 or 2 harmonics (3 are not instantiated, 0 have no velocity), "
+                         f"got {nu.shape}")
+    if len(counts.shape) != 2 or counts.shape[0] < 1 or counts.shape[1] < 1:
+        raise ValueError("counts must be [cells, genes] with at least one of each")
+    Nc, Ng = int(counts.shape[0]), int(counts.shape[1])
+    if nu.shape[1] != Ng:
+        raise ValueError(f"means has {nu.shape[1]} genes, counts {Ng}")
+    xy = np.asarray(directions, dtype=np.float64)
+    if xy.shape != (2, Nc):
+        raise ValueError(f"directions must be [2, cells] = (2, {Nc}) like Phases.phi_xy, got {xy.shape}")
+    norm2 = xy[0] ** 2 + xy[1] ** 2
+    if not (np.isfinite(norm2).all() and (norm2 > 0).all()):
+        raise ValueError("every cell needs a finite phase direction of non-zero length")
+    n = np.asarray(n_scounts, dtype=np.float64).reshape(-1)
+    if n.size != Nc:
+        raise ValueError(f"n_scounts has {n.size} entries for {Nc} cells")
+    if not (np.isfinite(n).all() and (n > 0).all()):
+        raise ValueError("every cell needs a finite n_scounts > 0")
+    if not (tol >= 0):
+        raise ValueError("tol must be >= 0")
+    if int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError("max_iter must be an integer >= 1")
+    r = None
+    if noisemodel == "NegativeBinomial":
+        d = torch.as_tensor(np.asarray(dispersion, dtype=np.float64)).reshape(-1)
+        if d.numel() not in (1, Ng):
+            raise ValueError(f"dispersion must be a scalar or one value per gene ({Ng}), got {d.numel()}")
+        if not bool((torch.isfinite(d) & (d > 0)).all()):
+            raise ValueError("dispersion must be > 0")
+        r = (1.0 / d).expand(Ng).contiguous()
+    if prior is None or len(prior) != 4:
+        raise ValueError("the prior is (mu_gamma, sd_gamma, mu_beta, sd_beta) of log gamma and log beta")
+    cols = []
+    for v in prior:
+        t = np.asarray(v, dtype=np.float64).reshape(-1)
+        if t.size not in (1, Ng):
+            raise ValueError(f"the prior's entries must be scalars or one value per gene ({Ng}), got {t.size}")
+        cols.append(np.broadcast_to(t, (Ng,)))
+    pr = np.ascontiguousarray(np.stack(cols, 1))
+    if not (pr[:, 1] > 0).all() or not (pr[:, 3] > 0).all():
+        raise ValueError("the prior's standard deviations must be > 0")
+    if evaluate_only and start is None:
+        raise ValueError("evaluate_only needs start: the (log gamma, log beta) to evaluate at")
+    st = None
+    if start is not None:
+        st = np.asarray(start, dtype=np.float64)
+        if st.shape != (2, Ng):
+            raise ValueError(f"start must be [2, genes] = (2, {Ng}): rows log gamma, log beta; got {st.shape}")
+        st = np.ascontiguousarray(st.T)
+    basis = fourier_basis_from_directions(xy, (nu.shape[0] - 1) // 2)
+    logm = float(a) * torch.log(torch.as_tensor(n))
+    return basis, logm, np.ascontiguousarray(nu.T), r, pr, st
+
+
+def _check_omega(omega, Nc):
+    om = np.asarray(omega, dtype=np.float64).reshape(-1)
+    if om.size == 1:
+        om = np.broadcast_to(om, (Nc,))
+    if om.size != Nc:
+        raise ValueError(f"omega must be a scalar or one value per cell ({Nc}), got {om.size}")
+    if not np.isfinite(om).all():
+        raise ValueError("omega must be finite")
+    return np.ascontiguousarray(om)
+
+
+class _Problem:
+    """The genes staged on the device in chunks (kept for every call of an outer iteration) and the kernel's launches over them."""
+
+    def __init__(self, counts, basis, logm, nu, r, prior, noisemodel, device, chunk_genes, storage):
+        self.lib, self.dev, self.Error = _open_device(device)
+        self.Nc, self.Ng, self.K = int(counts.shape[0]), int(counts.shape[1]), int(basis.shape[0])
+        self.noise = _lib.NOISE[noisemodel]
+        dev = self.dev
+        if _is_sparse(counts):
+            counts = counts.tocsc()
+        with torch.cuda.device(dev):
+            self.B = basis.to(torch.float32).to(dev).contiguous()
+            self.logm = logm.to(torch.float32).to(dev).contiguous()
+            self.nu = torch.as_tensor(nu).to(dev).contiguous()
+            self.r = r.to(torch.float32).to(dev).contiguous() if r is not None else None
+            r64 = self.r.double() if self.r is not None else None                # the model is the one of the float32 r the kernel reads
+            self.prior = torch.as_tensor(prior).to(dev).contiguous()
+            self.const = torch.empty(self.Ng, dtype=torch.float64, device=dev)
+            step = int(chunk_genes) if chunk_genes is not None else default_chunk_genes(self.Nc)
+            self.chunks = []
+            for g0 in range(0, self.Ng, step):
+                g1 = min(self.Ng, g0 + step)
+                blk, kblk, kind = _stage(counts, g0, g1, self.Nc, dev, storage)
+                self.const[g0:g1] = _constants(blk, r64[g0:g1] if r64 is not None else None)
+                self.chunks.append((g0, g1, kblk, kind))
+                del blk
+
+    def run(self, W, nuw, start, tol, max_iter):
+        """One launch per chunk at the design W (float32 device [NW, Nc]) and the coefficients nuw (host float64 [NW]).  Returns device
+        tensors over all genes: xy [Ng, 2], cov [Ng, 3], ll, dec, it, st, nc, score [Ng, NW], info [Ng, NW (NW + 1) / 2]."""
+        dev, Ng, NW = self.dev, self.Ng, int(W.shape[0])
+        NWH = NW * (NW + 1) // 2
+        with torch.cuda.device(dev):
+            nuw_d = torch.as_tensor(np.ascontiguousarray(nuw, dtype=np.float64)).to(dev)
+            start_d = torch.as_tensor(start).to(dev).contiguous() if start is not None and not torch.is_tensor(start) else start
+            f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)         # noqa: E731
+            i32 = lambda: torch.empty(Ng, dtype=torch.int32, device=dev)             # noqa: E731
+            out = dict(xy=f64(Ng, 2), cov=f64(Ng, 3), ll=f64(Ng), dec=f64(Ng), it=i32(), st=i32(), nc=i32(), score=f64(Ng, max(NW, 1)),
+                       info=f64(Ng, max(NWH, 1)))
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            for g0, g1, kblk, kind in self.chunks:
+                sl = lambda t: _ptr(t[g0:g1]) if t is not None else None             # noqa: E731
+                rc = self.lib.vc_gene_kinetics(_ptr(kblk), kind, g1 - g0, self.Nc, self.Nc, _ptr(self.B), self.K, _ptr(self.logm),
+                                               sl(self.nu), _ptr(W) if NW else None, NW, _ptr(nuw_d) if NW else None, self.noise,
+                                               sl(self.r), sl(self.prior), sl(start_d), float(tol), int(max_iter), sl(out["xy"]),
+                                               sl(out["cov"]), sl(out["ll"]), sl(out["dec"]), sl(out["it"]), sl(out["st"]), sl(out["nc"]),
+                                               sl(out["score"]) if NW else None, sl(out["info"]) if NW else None, stream)
+                if rc != _lib.VC_OK:
+                    raise self.Error(f"vc_gene_kinetics failed ({rc}): {self.lib.vc_last_error(None).decode()}")
+            torch.cuda.current_stream(dev).synchronize()                             # nuw_d and the slices outlive their launches
+            out["score"], out["info"] = out["score"][:, :NW], out["info"][:, :NWH]
+        return out
+
+    def penalty(self, xy):
+        """The genes' Gaussian penalties at xy, device float64 [Ng]."""
+        p = self.prior
+        return 0.5 * ((xy[:, 0] - p[:, 0]) / p[:, 1]) ** 2 + 0.5 * ((xy[:, 1] - p[:, 2]) / p[:, 3]) ** 2
+
+    def fit(self, out):
+        NW = out["score"].shape[1]
+        tri = torch.tril_indices(NW, NW)
+        info = torch.zeros((self.Ng, NW, NW), dtype=torch.float64, device=self.dev)
+        info[:, tri[0], tri[1]] = out["info"]
+        info[:, tri[1], tri[0]] = out["info"]
+        c = out["cov"]
+        cov = torch.stack([torch.stack([c[:, 0], c[:, 1]], 1), torch.stack([c[:, 1], c[:, 2]], 1)], 1)
+        return GeneKineticsFit(log_gamma=out["xy"][:, 0].cpu().numpy().copy(), log_beta=out["xy"][:, 1].cpu().numpy().copy(),
+                               cov=cov.cpu().numpy(), stds=torch.sqrt(torch.stack([c[:, 0], c[:, 2]])).cpu().numpy(),
+                               loglik=(out["ll"] + self.const).cpu().numpy(), decrement=out["dec"].cpu().numpy(),
+                               iterations=out["it"].cpu().numpy(), status=out["st"].cpu().numpy(), n_clamped=out["nc"].cpu().numpy(),
+                               score_w=out["score"].cpu().numpy().copy(), info_w=info.cpu().numpy())
+
+
+def gene_kinetics(counts_U, directions, n_scounts, means, omega=None, a=1, noisemodel="Poisson", dispersion=0.3, *, prior=DEFAULT_PRIOR,
+                  start=None, evaluate_only=False, tol=1e-10, max_iter=25, device=None, chunk_genes=None, storage="auto", nu_omega=None,
+                  harmonics_w=0, condition_design=None):
+    """(log gamma, log beta) of every gene at the angular speed `omega` (a scalar or one value per cell), on the HIP kernel
+    `vc_gene_kinetics`: the maximum over both of the unspliced counts' log-likelihood under the model's Normal priors
+    `prior = (mu_gamma, sd_gamma, mu_beta, sd_beta)` (scalars or one value per gene).  counts_U: [Nc, Ng] like an AnnData layer (numpy,
+    scipy sparse or torch); directions, n_scounts, a, dispersion, device, chunk_genes, storage: as for `gene_harmonics` (same staging,
+    chunking and truncation); means: [2H+1, Ng] like `Cycle.means`, H in {1, 2}.  start: [2, Ng] (rows log gamma, log beta) the
+    iteration starts from; evaluate_only=True makes one pass at `start`.  A gene without a count, or with a coefficient that is not
+    finite, comes back NO_DATA with NaN outputs.  Returns a `GeneKineticsFit`; its score_w / info_w are those of a common factor on
+    omega (the design's one row is omega itself).  With omega=None the speed is that of the coefficients `nu_omega` (condition-major,
+    [Nx (2 Hω + 1)]) on the design of `harmonics_w` and `condition_design` (`omega_design`), and score_w / info_w are theirs."""
+    basis, logm, nu, r, pr, st = check_arguments(counts_U, directions, n_scounts, means, a, noisemodel, dispersion, prior, start,
+                                                 evaluate_only, tol, max_iter)
+    if (omega is None) == (nu_omega is None):
+        raise ValueError("give either omega (per cell) or nu_omega (coefficients on the design of harmonics_w and condition_design)")
+    if omega is not None:
+        W64, nuw = _check_omega(omega, int(counts_U.shape[0]))[None, :], np.ones(1)
+    else:
+        W64 = omega_design(directions, harmonics_w, condition_design)
+        nuw = np.asarray(nu_omega, dtype=np.float64).reshape(-1)
+        if nuw.shape != (W64.shape[0],) or not np.isfinite(nuw).all():
+            raise ValueError(f"nu_omega must be {W64.shape[0]} finite coefficients (condition-major)")
+    _check_run_options(storage, chunk_genes)
+    prob = _Problem(counts_U, basis, logm, nu, r, pr, noisemodel, device, chunk_genes, storage)
+    with torch.cuda.device(prob.dev):
+        W = torch.as_tensor(W64).to(torch.float32).to(prob.dev).contiguous()
+        return prob.fit(prob.run(W, nuw, st, tol, 0 if evaluate_only else max_iter))
+
+
+def omega_design(directions, harmonics_w=0, condition_design=None):
+    """W float64 [Nx (2 Hω + 1), Nc]: row x (2 Hω + 1) + h is the indicator of condition x times row h of zeta_omega(phi)
+    (utils.torch_fourier_basis at Hω harmonics, formed from the directions).  condition_design: [Nx, Nc] or None (one condition)."""
+    xy = np.asarray(directions, dtype=np.float64)
+    if int(harmonics_w) != harmonics_w or harmonics_w < 0:
+        raise ValueError("the angular speed's harmonics must be an integer >= 0")
+    Nc = xy.shape[1]
+    D = np.ones((1, Nc)) if condition_design is None else np.asarray(condition_design, dtype=np.float64)
+    if D.ndim != 2 or D.shape[1] != Nc or D.shape[0] < 1:
+        raise ValueError(f"condition_design must be [conditions, cells] = (Nx, {Nc}), got {D.shape}")
+    if not np.isfinite(D).all():
+        raise ValueError("condition_design must be finite")
+    zeta = fourier_basis_from_directions(xy, int(harmonics_w)).numpy()
+    NW = D.shape[0] * zeta.shape[0]
+    if NW > MAX_NW:
+        raise ValueError(f"{D.shape[0]} conditions x {zeta.shape[0]} rows of zeta_omega = {NW} coefficients of the angular speed; "
+                         f"at most {MAX_NW} are instantiated")
+    return (D[:, None, :] * zeta[None, :, :]).reshape(NW, Nc)
+
+
+def _nuw_prior(prior, Nx, Nhw):
+    """(means, precisions) float64 [NW], condition-major, from an `AngularSpeed` (or None: its `trivial_prior`)."""
+    if prior is None:
+        from .containers import AngularSpeed
+        prior = AngularSpeed.trivial_prior(list(range(Nx)), harmonics=(Nhw - 1) // 2)
+    m, s = np.asarray(prior.means.values, dtype=np.float64), np.asarray(prior.stds.values, dtype=np.float64)
+    if m.shape != (Nhw, Nx) or s.shape != (Nhw, Nx):
+        raise ValueError(f"the angular speed's prior must be [2 Hω + 1, conditions] = ({Nhw}, {Nx}), got {m.shape}")
+    if not (np.isfinite(m).all() and np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError("the angular speed's prior needs finite means and finite stds > 0")
+    return np.ascontiguousarray(m.T).reshape(-1), 1.0 / np.ascontiguousarray(s.T).reshape(-1) ** 2
+
+
+def _solve_spd(J, G):
+    L = np.linalg.cholesky(J)
+    return np.linalg.solve(L.T, np.linalg.solve(L, G))
+
+
+def velocity_map(counts_U, directions, n_scounts, means, harmonics_w=0, condition_design=None, a=1, noisemodel="Poisson", dispersion=0.3,
+                 *, prior=DEFAULT_PRIOR, nuw_prior=None, nuw_start=None, tol=1e-10, max_iter=25, tol_outer=1e-8, max_rounds=30,
+                 device=None, chunk_genes=None, storage="auto"):
+    """The MAP angular speed with every gene's kinetics profiled out:  F(νω) = sum_g max f_g(x, y; νω) - sum_i (νω_i - m_i)^2 / 2 s_i^2,
+    `nuw_prior` an `AngularSpeed` over the conditions at `harmonics_w` harmonics (None: its `trivial_prior`).  Per round one
+    `vc_gene_kinetics` call per chunk, warm-started from the previous (x, y); the genes' values are summed in float64 by halving;
+    G = sum score - Λ (νω - m), J = sum info + Λ, step = J^-1 G, dec = G . step <= tol_outer -> CONVERGED.  A trial point is halved
+    while F drops by more than its rounding (8 eps32 sum_g |L_g|), at most 10 times (then STALLED); `max_rounds` steps -> MAX_ROUNDS.
+    Genes whose first-round status is not CONVERGED or ROUNDING are left out from then on (`n_excluded`); one that fails later ends
+    the fit with GENE_FAILED.  Returns a `VelocityMapFit`."""
+    basis, logm, nu, r, pr, _ = check_arguments(counts_U, directions, n_scounts, means, a, noisemodel, dispersion, prior, None, False,
+                                                tol, max_iter)
+    W64 = omega_design(directions, harmonics_w, condition_design)
+    Nhw = 2 * int(harmonics_w) + 1
+    NW, Nx = W64.shape[0], W64.shape[0] // Nhw
+    pm, pp = _nuw_prior(nuw_prior, Nx, Nhw)
+    if not (tol_outer >= 0):
+        raise ValueError("tol_outer must be >= 0")
+    if int(max_rounds) != max_rounds or max_rounds < 0:
+        raise ValueError("max_rounds must be an integer >= 0")
+    nuw = pm.copy() if nuw_start is None else np.asarray(nuw_start, dtype=np.float64).reshape(-1).copy()
+    if nuw.shape != (NW,) or not np.isfinite(nuw).all():
+        raise ValueError(f"nuw_start must be {NW} finite coefficients (condition-major)")
+    _check_run_options(storage, chunk_genes)
+    prob = _Problem(counts_U, basis, logm, nu, r, pr, noisemodel, device, chunk_genes, storage)
+    ok_codes = (_lib.VC_KIN_CONVERGED, _lib.VC_KIN_ROUNDING)
+    with torch.cuda.device(prob.dev):
+        W = torch.as_tensor(W64).to(torch.float32).to(prob.dev).contiguous()
+        zero = torch.zeros((), dtype=torch.float64, device=prob.dev)
+
+        def evaluate(v, start, inc):
+            o = prob.run(W, v, start, tol, max_iter)
+            good = (o["st"] == ok_codes[0]) | (o["st"] == ok_codes[1])
+            inc = good if inc is None else inc
+            f = torch.where(inc, o["ll"] + prob.const - prob.penalty(o["xy"]), zero)
+            mag = torch.where(inc, o["ll"].abs(), zero)
+            sums = _row_sums(torch.cat([f[None, :], mag[None, :], torch.where(inc[:, None], o["score"], zero).T,
+                                        torch.where(inc[:, None], o["info"], zero).T]).contiguous()).cpu().numpy()
+            J = np.zeros((NW, NW))
+            J[np.tril_indices(NW)] = sums[2 + NW:]
+            J = J + np.tril(J, -1).T + np.diag(pp)
+            d = v - pm
+            return dict(out=o, inc=inc, failed=bool((inc & ~good).any()), F=float(sums[0] - 0.5 * (pp * d * d).sum()),
+                        allow=8.0 * EPS32 * float(sums[1]), G=sums[2:2 + NW] - pp * d, J=J)
+
+        cur = evaluate(nuw, None, None)
+        inc = cur["inc"]
+        n_excluded = int((~inc).sum())
+        status, rounds, dec = "MAX_ROUNDS", 0, float("nan")
+        if n_excluded == prob.Ng:
+            status = "GENE_FAILED"
+        else:
+            while True:
+                step = _solve_spd(cur["J"], cur["G"])
+                dec = float(cur["G"] @ step)
+                if dec <= tol_outer:
+                    status = "CONVERGED"
+                    break
+                if rounds >= max_rounds:
+                    status = "MAX_ROUNDS"
+                    break
+                t, moved = 1.0, False
+                for _ in range(MAX_OUTER_HALVINGS + 1):
+                    trial = evaluate(nuw + t * step, cur["out"]["xy"], inc)
+                    if trial["failed"]:
+                        status = "GENE_FAILED"
+                        break
+                    if trial["F"] >= cur["F"] - max(cur["allow"], trial["allow"]):
+                        nuw, cur, moved = nuw + t * step, trial, True
+                        break
+                    t *= 0.5
+                else:
+                    status = "STALLED"
+                if not moved:
+                    break
+                rounds += 1
+        cov = np.linalg.inv(cur["J"])
+        table = lambda v: np.ascontiguousarray(v.reshape(Nx, Nhw).T)                 # noqa: E731
+        return VelocityMapFit(nu_omega=table(nuw), stds=table(np.sqrt(np.diag(cov))), cov=cov, F=cur["F"], dec=dec, rounds=rounds,
+                              status=status, n_excluded=n_excluded, included=inc.cpu().numpy(), kinetics=prob.fit(cur["out"]))
