@@ -282,7 +282,11 @@ int vc_set_counts(vc_engine* e, const float* S, const float* U, int64_t gene_str
  * layers hold before the reference densifies them (preprocessing.py:141-147 `.A`, 243-252).  which: 0 = spliced,
  * 1 = unspliced (velocity model).  indptr int64[Nc_local + 1], indices int32[nnz], data float[nnz]; on_device as above
  * (device arrays must stay valid until vc_finalize has returned).  The dense matrix is never formed on the host: the
- * blocked HBM layout is filled by a scatter kernel that also builds the per-gene count histograms. */
+ * blocked HBM layout is filled by a scatter kernel that also builds the per-gene count histograms.
+ * Host arrays (on_device = 0) are validated here: indptr[0] == 0, indptr[Nc_local] == nnz, indptr non-decreasing; gene
+ * indices and values are checked by the scatter kernel (vc_finalize returns VC_ERR_ARG).  On-device arrays
+ * (on_device = 1) are TRUSTED: indptr is not read back or validated, and an indptr that is inconsistent with nnz makes
+ * the scatter kernel read out of bounds.  The Python package never takes that path. */
 int vc_set_counts_csr(vc_engine* e, int which, const int64_t* indptr, const int32_t* indices, const float* data,
                       int64_t nnz, int on_device);
 /* count_factor (Nc_local), D (Nx, Nc_local) row-major [NULL for phase], Db (Nb, Nc_local) row-major

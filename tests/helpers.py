@@ -77,6 +77,11 @@ def problem_from_spec(spec, dtype=torch.float64) -> orc.Problem:
         if k in ("truth", "S_csr", "U_csr"):
             continue
         kw[k] = v.detach().cpu().to(dtype) if (isinstance(v, torch.Tensor) and v.is_floating_point()) else v
+    # a spec that carries its counts as CSR only (cells x genes; what the engine then ingests): the oracle gets them densified
+    # (callers also pass an oracle Problem, which has no such fields)
+    for k, csr in (("S", getattr(spec, "S_csr", None)), ("U", getattr(spec, "U_csr", None))):
+        if kw.get(k) is None and csr is not None:
+            kw[k] = torch.tensor(np.asarray(csr.toarray(), dtype=np.float64).T.copy()).to(dtype)
     kw["condition_on"] = {k: v.detach().cpu().to(dtype) for k, v in spec.condition_on.items()}
     return orc.Problem(**kw)
 
@@ -711,3 +716,87 @@ def nb_shape_inv_terms(spec, par, eps):
         tables.append(t)
     scale += np.abs((spec.gamma_alpha - 1.0) - spec.gamma_beta * si)
     return r, scale, tables
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Count ingest: the blocked count layout and the per-gene histograms are filled by vc_pack_counts_kernel (dense input) or
+# vc_scatter_csr_kernel (CSR input).  The oracle is handed the same matrix as the engine, not what the engine stored, so the
+# bar between two ingest forms of one matrix is equality of engines (tests/test_hip_ingest.py, tests/test_hip_ingest_paths.py).
+# ---------------------------------------------------------------------------------------------------------------------
+def _mk(spec, **kw):
+    from velocycle_amd.engine import HipEngine
+    return HipEngine(spec, **kw)
+
+
+def _hist_equal(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def _host_checker(spec, tuning=None, **kw):
+    from velocycle_amd.tuning import Tuning
+    e = _mk(spec, tuning=(tuning or Tuning()).replace(host_hist=True), **kw)
+    assert not e.stats["hist_on_device"]
+    return e
+
+
+SPARSE_EDGE_ROW_LENGTHS = (1, 63, 64, 65, 129, 200)     # around the 64 lanes of the scatter kernel's wave, and past two trips
+SPARSE_EDGE_EMPTY_GENE = 5
+
+
+def sparse_edge_counts(Nc, Ng, seed):
+    """(dense, csr): counts of Nc cells x Ng genes (Ng >= 260, Nc >= 3 * (len(SPARSE_EDGE_ROW_LENGTHS) + 3)) as a NON-canonical
+    scipy CSR matrix built from (data, indices, indptr) -- what a caller may hand to the engine -- and the dense (Nc, Ng) float32
+    matrix it stands for: the float64 sum of the stored entries of every (cell, gene), cast to float32.  Planted:
+      * cells 0 and Nc - 1 and, of the middle shard of a 3-way split (engine.shard_bounds(Nc, 1, 3)), the first and the last cell
+        without any stored entry;
+      * rows of exactly SPARSE_EDGE_ROW_LENGTHS stored entries, distinct genes, once from cell 1 on (ascending indices) and once from
+        the second cell of the middle shard on (indices stored in DESCENDING order); the 200-entry rows hold the last gene Ng - 1;
+      * gene SPARSE_EDGE_EMPTY_GENE without any entry;
+      * every other cell: ~8 % of the genes with counts 1 .. 12, indices in random order; 24 of these rows get an explicitly
+        stored 0.0 at a gene they do not hold otherwise, 24 others one (cell, gene) entry stored TWICE (a + b: the values add).
+    The planted-length rows have neither zeros nor duplicates: their lengths are what the kernel sees after sum_duplicates()."""
+    from velocycle_amd.engine import shard_bounds
+    rng = np.random.default_rng(seed)
+    c0, c1 = shard_bounds(Nc, 1, 3)
+    empty = {0, Nc - 1, c0, c1 - 1}
+    genes = np.array([g for g in range(Ng) if g != SPARSE_EDGE_EMPTY_GENE])
+    planted = {}
+    for start, descending in ((1, False), (c0 + 1, True)):
+        for i, n in enumerate(SPARSE_EDGE_ROW_LENGTHS):
+            planted[start + i] = (n, descending)
+    assert not (set(planted) & empty) and max(planted) < Nc - 1 and len(planted) == 2 * len(SPARSE_EDGE_ROW_LENGTHS)
+    plain = [c for c in range(Nc) if c not in empty and c not in planted]
+    special = rng.permutation(plain)[:48]
+    zeros, dups = set(special[:24].tolist()), set(special[24:].tolist())
+    indptr, indices, data = [0], [], []
+    for c in range(Nc):
+        if c in empty:
+            idx, val = np.zeros(0, np.int64), np.zeros(0)
+        elif c in planted:
+            n, descending = planted[c]
+            idx = np.sort(rng.choice(genes[:-1], size=n - (n >= 200), replace=False))
+            if n >= 200:
+                idx = np.append(idx, Ng - 1)
+            idx = idx[::-1] if descending else idx
+            val = rng.integers(1, 13, size=idx.size).astype(np.float64)
+        else:
+            idx = rng.permutation(genes[rng.random(genes.size) < 0.08])
+            if idx.size < 2:
+                idx = rng.choice(genes, size=2, replace=False)
+            val = rng.integers(1, 13, size=idx.size).astype(np.float64)
+            if c in zeros:
+                free = np.setdiff1d(genes, idx)
+                at = int(rng.integers(0, idx.size + 1))
+                idx, val = np.insert(idx, at, rng.choice(free)), np.insert(val, at, 0.0)
+            if c in dups:
+                k = int(rng.integers(0, idx.size))
+                idx, val = np.append(idx, idx[k]), np.append(val, float(rng.integers(1, 13)))
+        indices.append(idx)
+        data.append(val)
+        indptr.append(indptr[-1] + idx.size)
+    indices, data = np.concatenate(indices), np.concatenate(data)
+    dense = np.zeros((Nc, Ng), dtype=np.float64)
+    np.add.at(dense, (np.repeat(np.arange(Nc), np.diff(indptr)), indices), data)
+    import scipy.sparse as sp
+    csr = sp.csr_matrix((data.astype(np.float32), indices.astype(np.int32), np.asarray(indptr, dtype=np.int64)), shape=(Nc, Ng))
+    return dense.astype(np.float32), csr

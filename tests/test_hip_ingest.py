@@ -12,24 +12,9 @@ import scipy.sparse as sp
 import torch
 
 from tests import helpers as H
+from tests.helpers import _hist_equal, _host_checker, _mk      # (shared with tests/test_hip_ingest_paths.py)
 
 pytestmark = pytest.mark.gpu
-
-
-def _mk(spec, **kw):
-    from velocycle_amd.engine import HipEngine
-    return HipEngine(spec, **kw)
-
-
-def _hist_equal(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def _host_checker(spec, tuning=None, **kw):
-    from velocycle_amd.tuning import Tuning
-    e = _mk(spec, tuning=(tuning or Tuning()).replace(host_hist=True), **kw)
-    assert not e.stats["hist_on_device"]
-    return e
 
 
 @pytest.mark.parametrize("case", ["vel_mf_joint", "phase_nb", "vel_lrmn_cond_dnu2", "vel_mf_poisson"])
