@@ -38,6 +38,8 @@
  *   vc_gene_glm                 no counterpart (a host loop of one GLM per gene would be it): the model of Phases.from_cycle_mle
  *                               (phases.py:487-507) solved for the gene harmonics with the phases known -- a Poisson or
  *                               negative-binomial log-link regression on the Fourier design per gene; stand-alone, no engine
+ *   vc_gene_glm_batch           no counterpart: vc_gene_glm with the phase model's per-batch offsets (phase_inference_model.py: ElogS =
+ *                               nu . zeta + Db . dnu + count_factor), nu and dnu estimated jointly per gene; stand-alone, no engine
  *   vc_gene_dispersion          no counterpart (the reference learns shape_inv only inside the SVI, velocity_inference_model.py:383):
  *                               the maximum-likelihood (or Gamma-prior mode) negative-binomial dispersion per gene with the means of
  *                               vc_gene_glm known; stand-alone, no engine
@@ -556,6 +558,42 @@ int vc_gene_glm(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, 
                 const float* logm_dev, int noise, const float* r_dev, const double* prior_mean_dev, const double* prior_prec_dev,
                 double tol, int max_iter, double* nu_dev, double* cov_dev, double* loglik_dev, double* dec_dev,
                 int32_t* iterations_dev, int32_t* status_dev, void* hip_stream);
+
+/* --- per-gene harmonic regression with per-batch offsets (stand-alone: no engine handle) --------------------------------------
+ * vc_gene_glm with the phase model's batch factor, ElogS = nu . zeta(phi) + Db . dnu + count_factor: per gene, nu (K coefficients) and
+ * one offset delta_b per batch are estimated jointly,
+ *   eta_c = nu . basis[:, c] + delta_b(c) + logm[c],   mu = exp(eta),
+ * by maximising vc_gene_glm's Poisson / negative-binomial objective minus sum_b q_b (delta_b - m_b)^2 / 2 (and minus the optional
+ * Gaussian prior of nu).  Every delta_b ALWAYS has its prior: it is what separates nu_0 from the mean of delta.  One workgroup per
+ * gene, one launch, no workspace, no allocation, no synchronisation; asynchronous on hip_stream.  counts_dev, count_kind, Ng, Nc,
+ * gene_stride, basis_dev, K, logm_dev, noise, r_dev, prior_mean_dev, prior_prec_dev, tol, max_iter: as for vc_gene_glm.
+ *   Nb, seg_host    the cells of a batch are contiguous: batch b owns the cells [seg[b], seg[b + 1]).  seg_host is int64_t[Nb + 1] in
+ *                   HOST memory (it is checked here and travels in the kernel's arguments): seg[0] = 0, seg[Nb] = Nc, strictly
+ *                   increasing (an empty segment is refused); 1 <= Nb <= VC_GLM_MAX_BATCHES
+ *   delta_prior_mean_dev, delta_prior_prec_dev   double[Ng][Nb] in device memory, never NULL: m_b and q_b = 1 / std_b^2.  A gene with
+ *                   an m_b that is not finite or a q_b that is not a positive finite number ends VC_GLM_SINGULAR (device memory is not
+ *                   read before the launch)
+ * Per-element arithmetic and every sum are vc_gene_glm's; a pass walks the segments in order and folds after each, the (K + Nb)-square
+ * Newton system is solved through the Schur complement of its diagonal delta block in float64.  Identical bits under repetition,
+ * uint16 or float32 storage and any cutting of the genes into calls.  Rules and status codes are vc_gene_glm's over the K + Nb
+ * coefficients: start nu_0 = ln(sum k / sum e^logm), harmonics 0 (their prior means), delta = m; VC_GLM_CONVERGED on the full
+ * decrement g' H^-1 g <= tol; VC_GLM_ROUNDING when every one of the K + Nb gradient entries is within 4 eps32 sqrt(N_i);
+ * VC_GLM_UNBOUNDED when a harmonic or a delta_b of a step leaves [-50, 50], or the gene has no count; VC_GLM_SINGULAR when a pivot of
+ * the Schur complement or a D_b = sum_{c in b} w + q_b is not a positive finite number; VC_GLM_MAX_ITER (or 30 halvings of the
+ * penalised objective used up).  Outputs per gene, of the last accepted point:
+ *   nu_dev          double[Ng][K];   delta_dev  double[Ng][Nb]
+ *   cov_nu_dev      double[Ng][K (K + 1) / 2]: the nu block of the inverse Hessian, packed as vc_gene_glm's cov_dev; NaN when SINGULAR
+ *   delta_var_dev   double[Ng][Nb]: the diagonal of the delta block of the inverse Hessian; NaN when SINGULAR
+ *   loglik_dev      the objective without any prior term;  dec_dev, iterations_dev, status_dev: as for vc_gene_glm
+ * A gene's status touches no other gene's outputs; every path is bounded.  VC_ERR_ARG (vc_gene_glm's, Nb out of range, a NULL seg_host
+ * or delta prior, a seg that does not start at 0, end at Nc or increase strictly): all decided before anything is launched. */
+#define VC_GLM_MAX_BATCHES 32
+int vc_gene_glm_batch(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* basis_dev, int K,
+                      const float* logm_dev, int noise, const float* r_dev, int Nb, const int64_t* seg_host,
+                      const double* delta_prior_mean_dev, const double* delta_prior_prec_dev, const double* prior_mean_dev,
+                      const double* prior_prec_dev, double tol, int max_iter, double* nu_dev, double* delta_dev, double* cov_nu_dev,
+                      double* delta_var_dev, double* loglik_dev, double* dec_dev, int32_t* iterations_dev, int32_t* status_dev,
+                      void* hip_stream);
 
 /* --- per-gene negative-binomial dispersion given the means (stand-alone: no engine handle) -----------------------------------
  * The third factor of the model of vc_gene_glm: with eta_c = nu_g . basis[:, c] + logm[c], mu = exp(eta) known, maximise over

@@ -23,6 +23,7 @@ GUIDE = {"meanfield": 0, "lrmn": 1}
 NOISE = {"NegativeBinomial": 0, "Poisson": 1, "Lognormal": 2}
 VC_COUNTS_F32, VC_COUNTS_U16 = 0, 1
 VC_GLM_CONVERGED, VC_GLM_ROUNDING, VC_GLM_UNBOUNDED, VC_GLM_SINGULAR, VC_GLM_MAX_ITER = 0, 1, 2, 3, 4
+VC_GLM_MAX_BATCHES = 32
 VC_DISP_CONVERGED, VC_DISP_ROUNDING, VC_DISP_AT_UPPER, VC_DISP_AT_LOWER, VC_DISP_MAX_ITER, VC_DISP_EVALUATED, VC_DISP_NO_DATA = range(7)
 VC_KIN_CONVERGED, VC_KIN_ROUNDING, VC_KIN_MAX_ITER, VC_KIN_UNBOUNDED, VC_KIN_NO_DATA, VC_KIN_EVALUATED = range(6)
 VC_DISP_RHO_MIN, VC_DISP_RHO_MAX =-6.907755278982137, 13.815510557964274           # ln 1e-3, ln 1e6
@@ -139,6 +140,9 @@ EXPORTS = {
     "vc_gene_glm": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p]),
+    "vc_gene_glm_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vc_gene_dispersion": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -176,6 +176,46 @@ class Cycle(_HarmonicTable):
             out.set_disp_pyro(fit.dispersion)
         return (out, fit) if return_fit else out
 
+    @classmethod
+    def from_phases_batch_mle(cls, phases, data, batch_design, harmonics=1, a=1, noisemodel='Poisson', dispersion=0.3, *,
+                              layer='spliced', delta_nu_prior=(0.0, 0.5), prior=None, return_fit=False, **worker_kw):
+        """`from_phases_mle` for data pooled from several samples: the phase model's per-batch offsets (ElogS = nu . zeta(phi) +
+        Db . dnu + count_factor, dnu ~ Normal(mu_dnu, sigma_dnu)) are estimated jointly with the harmonics of every gene, by the HIP
+        kernel behind `velocycle_amd.gene_batch.gene_harmonics_batched`.  `batch_design`: the one-hot [cells, batches] matrix of
+        `make_design_matrix` (or an integer label per cell); `delta_nu_prior`: (mean, std) of the offsets, scalars or
+        [batches, genes].  `dispersion` is a number or one per gene ("mle" is refused).  Returns a Cycle, or with `return_fit=True`
+        (Cycle, GeneBatchHarmonicFit): the fit holds `delta_nu` / `delta_nu_stds` [batches, genes], which
+        `Phases.from_cycle_batch_mle` consumes, and the likelihood-ratio statistic for periodicity given the batches."""
+        from .gene_batch import gene_harmonics_batched
+        from .gene_harmonics import NOISEMODELS
+        if noisemodel not in NOISEMODELS:
+            raise NotImplementedError("Not implemented yet, sorry")
+        if layer not in data.layers:
+            raise ValueError(f"{layer=} is not a layer of the data")
+        counts = data.layers[layer]
+        Nc, Ng = counts.shape
+        cells_p, cells_d = list(phases.phi_xy.columns), list(data.obs.index)
+        named = not isinstance(phases.phi_xy.columns, pd.RangeIndex)
+        if phases.phi_xy.shape[1] != Nc or (named and cells_p != cells_d):
+            raise ValueError("the cells of the phases do not match the cells of the data (same cells, same order)")
+        genes = list(data.var.index)
+        prior_means = prior_stds = None
+        if prior is not None:
+            named = not isinstance(prior.means.columns, pd.RangeIndex)
+            if prior.means.shape[1] != Ng or (named and list(prior.means.columns) != genes):
+                raise ValueError("the genes of the prior do not match the genes of the data (same genes, same order)")
+            if prior.harmonics != harmonics:
+                raise ValueError(f"the prior has {prior.harmonics} harmonics, the fit {harmonics}")
+            prior_means = np.asarray(prior.means.values, dtype=np.float64)
+            prior_stds = np.asarray(prior.stds.values, dtype=np.float64)
+        if not (hasattr(counts, "tocsr") or torch.is_tensor(counts)):
+            counts = np.asarray(counts)
+        fit = gene_harmonics_batched(counts, np.asarray(phases.phi_xy.values, dtype=np.float64), np.asarray(data.obs.n_scounts.values),
+                                     batch_design, harmonics=harmonics, a=a, noisemodel=noisemodel, dispersion=dispersion,
+                                     delta_nu_prior=delta_nu_prior, prior_means=prior_means, prior_stds=prior_stds, **worker_kw)
+        out = cls.from_array(fit.means, fit.stds, gene_names=data.var.index)
+        return (out, fit) if return_fit else out
+
 
 def reorder(cycle: Cycle, gene_list):
     return Cycle.from_array(means_array=cycle.means[gene_list], stds_array=cycle.stds[gene_list])
@@ -400,6 +440,60 @@ class Phases:
         else:
             self.set_phixy(xy)
         return (best, prof) if return_profile else None
+
+    def from_cycle_batch_mle(self, cycle, data, batch_design, delta_nu, a=1, bins=100, concentration=10., noisemodel='Poisson',
+                             dispersion=0.3, *, device=None, chunk_cells=None):
+        """`from_cycle_mle` under given per-batch offsets `delta_nu` [batches, genes] (a `GeneBatchHarmonicFit.delta_nu`, or the SVI's
+        Δν means): the cells of batch b are assigned on the table T + delta_nu[b], one call of the same HIP grid kernel per batch on
+        that batch's cells, and the bins are scattered back.  `batch_design`: one-hot [cells, batches] or an integer label per cell.
+        In place like `from_cycle_mle`; with one batch and delta_nu = 0 it gives its bits."""
+        from .gene_batch import batch_labels
+        from .phase_mle import NOISEMODELS, phase_mle
+        from .utils import torch_fourier_basis, unpack_direction
+        if noisemodel not in NOISEMODELS:
+            raise NotImplementedError("Not implemented yet, sorry")
+        if int(bins) != bins or bins < 1:
+            raise ValueError("bins must be an integer >= 1")
+        bins = int(bins)
+        means = np.asarray(cycle.means.values, dtype=np.float64)
+        layer = data.layers['spliced']
+        Nc, Ng = layer.shape
+        genes_c, genes_d = list(cycle.means.columns), list(data.var.index)
+        named = not isinstance(cycle.means.columns, pd.RangeIndex)
+        if means.shape[1] != Ng or (named and genes_c != genes_d):
+            raise ValueError("the genes of the cycle do not match the genes of the data (same genes, same order)")
+        n_scounts = np.asarray(data.obs.n_scounts.values, dtype=np.float64)
+        if not (np.isfinite(n_scounts).all() and (n_scounts > 0).all()):
+            raise ValueError("every cell needs n_scounts > 0")
+        if noisemodel == 'NegativeBinomial' and not (np.asarray(dispersion, dtype=np.float64) > 0).all():
+            raise ValueError("dispersion must be > 0")
+        labels, Nb = batch_labels(batch_design, Nc)
+        dnu = np.asarray(delta_nu.detach().cpu().numpy() if torch.is_tensor(delta_nu) else delta_nu, dtype=np.float64)
+        if dnu.shape != (Nb, Ng):
+            raise ValueError(f"delta_nu must be [batches, genes] = ({Nb}, {Ng}), got {dnu.shape}")
+        if not np.isfinite(dnu).all():
+            raise ValueError("delta_nu must be finite")
+        phis = (2 * np.pi * torch.arange(0, 1, 1. / bins, dtype=torch.float32))[:bins]
+        basis = torch_fourier_basis(phis, num_harmonics=(means.shape[0] - 1) // 2)
+        T = basis.double() @ torch.tensor(means)
+        m = torch.tensor(n_scounts) ** float(a)
+        if not (hasattr(layer, "tocsr") or torch.is_tensor(layer)):
+            layer = np.asarray(layer)
+        elif hasattr(layer, "tocsr"):
+            layer = layer.tocsr()
+        best = torch.empty(Nc, dtype=torch.int64)
+        for b in range(Nb):
+            idx = np.flatnonzero(labels == b)
+            sub = layer[torch.as_tensor(idx)] if torch.is_tensor(layer) else layer[idx]
+            got, _ = phase_mle(sub, T + torch.tensor(dnu[b])[None, :], m[idx], noisemodel=noisemodel, dispersion=dispersion, device=device,
+                               chunk_cells=chunk_cells)
+            best[idx] = got.cpu()
+        xy = (concentration * unpack_direction(phis[best])).T
+        if self.phi_xy is None:
+            self.phi_xy = pd.DataFrame(xy.numpy(), index=["phi_x", "phi_y"], columns=data.obs.index)
+        else:
+            self.set_phixy(xy)
+        return None
 
     @classmethod
     def from_phase_marginal(cls, record, cell_names=None, concentration=None):
