@@ -102,6 +102,12 @@ def delta_prior(delta_nu_prior, Nb, Ng):
     return torch.as_tensor(np.ascontiguousarray(mean.T)), torch.as_tensor(np.ascontiguousarray(1.0 / std.T ** 2))
 
 
+def batch_segments(labels, Nb):
+    """(perm, seg): the stable permutation that makes the cells of a batch contiguous, batches in order, and the Nb + 1 segment bounds
+    (batch b owns the sorted cells [seg[b], seg[b + 1]))."""
+    return np.argsort(labels, kind="stable"), [0, *np.cumsum(np.bincount(labels, minlength=Nb)).tolist()]
+
+
 def gene_harmonics_batched(counts, directions, n_scounts, batches, harmonics=1, a=1, noisemodel="Poisson", dispersion=0.3, *,
                            delta_nu_prior=(0.0, 0.5), prior_means=None, prior_stds=None, tol=1e-10, max_iter=25, device=None,
                            chunk_genes=None, storage="auto"):
@@ -120,8 +126,8 @@ def gene_harmonics_batched(counts, directions, n_scounts, batches, harmonics=1, 
     Nc, Ng = int(counts.shape[0]), int(counts.shape[1])
     labels, Nb = batch_labels(batches, Nc)
     dm, dq = delta_prior(delta_nu_prior, Nb, Ng)
-    perm = np.argsort(labels, kind="stable")
-    seg = (C.c_int64 * (Nb + 1))(0, *np.cumsum(np.bincount(labels, minlength=Nb)).tolist())
+    perm, seg = batch_segments(labels, Nb)
+    seg = (C.c_int64 * (Nb + 1))(*seg)
     lib, dev, HipEngineError = _open_device(device)
     K = basis.shape[0]
     NH = K * (K + 1) // 2

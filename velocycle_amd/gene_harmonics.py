@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .phase_mle import CHUNK_BYTES, NOISEMODELS, _is_sparse
+from .phase_mle import CHUNK_BYTES, NOISEMODELS, _is_sparse, u16_bits
 
 MAX_HARMONICS = 3                    # csrc/vc_gene_glm.hip
 STATUS = {_lib.VC_GLM_CONVERGED: "CONVERGED", _lib.VC_GLM_ROUNDING: "ROUNDING", _lib.VC_GLM_UNBOUNDED: "UNBOUNDED",
@@ -279,9 +279,7 @@ def _stage(counts, g0, g1, Nc, dev, storage):
     if storage == "u16" and hi > 65535:
         raise ValueError("storage='u16' needs every count <= 65535")
     if storage != "f32" and hi <= 65535:
-        kblk = blk.to(torch.int32)
-        kblk[kblk >= 32768] -= 65536
-        return blk, kblk.to(torch.int16), _lib.VC_COUNTS_U16                     # the bits of the uint16 value
+        return blk, u16_bits(blk), _lib.VC_COUNTS_U16
     return blk, blk, _lib.VC_COUNTS_F32
 
 

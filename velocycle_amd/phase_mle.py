@@ -78,6 +78,23 @@ def _dense_block(counts, c0, c1, Ng, dev):
     return part.to(dev).to(torch.float32).T.clone(memory_format=torch.contiguous_format).trunc_()
 
 
+def u16_bits(blk):
+    """A float32 block of integers <= 65535 -> int16 holding the bits of the uint16 values (what VC_COUNTS_U16 reads)."""
+    blk = blk.to(torch.int32)
+    blk[blk >= 32768] -= 65536
+    return blk.to(torch.int16)
+
+
+def stage_tables(T, m, r):
+    """The float32 tables the kernel reads, on the host, from what `check_arguments` returns: (T - s, exp(T - s), m e^s, r or None).
+    mu = exp(T) m is unchanged by (T - s, m e^s): with s = mean(T) the kernel's tables are O(1) and its differences of logarithms
+    cancel a few digits less.  s depends on the cycle only, so every cell is still assigned independently of the others."""
+    s = T.mean()
+    Tc = T - s
+    return (Tc.to(torch.float32), torch.exp(Tc).to(torch.float32), (m * torch.exp(s)).to(torch.float32),
+            r.to(torch.float32) if r is not None else None)
+
+
 def phase_mle(counts, T, m, noisemodel="Poisson", dispersion=0.3, *, device=None, chunk_cells=None, return_profile=False,
               storage="auto"):
     """counts: [Nc, Ng] cell-major like an AnnData layer (numpy, scipy sparse or torch, host or device); T: [bins, Ng] log-rates per
@@ -96,15 +113,12 @@ def phase_mle(counts, T, m, noisemodel="Poisson", dispersion=0.3, *, device=None
         raise HipEngineError("velocycle_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
     dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
     bins = T.shape[0]
-    # mu = exp(T) m is unchanged by (T - s, m e^s): with s = mean(T) the kernel's tables are O(1) and its differences of logarithms
-    # cancel a few digits less.  s depends on the cycle only, so every cell is still assigned independently of the others.
-    s = T.mean()
-    Tc = T - s
+    T32, E32, m32, r32 = stage_tables(T, m, r)
     with torch.cuda.device(dev):
-        T_d = Tc.to(torch.float32).to(dev).contiguous()
-        E_d = torch.exp(Tc).to(torch.float32).to(dev).contiguous()
-        m_d = (m * torch.exp(s)).to(torch.float32).to(dev).contiguous()
-        r_d = r.to(torch.float32).to(dev).contiguous() if r is not None else None
+        T_d = T32.to(dev).contiguous()
+        E_d = E32.to(dev).contiguous()
+        m_d = m32.to(dev).contiguous()
+        r_d = r32.to(dev).contiguous() if r32 is not None else None
         best = torch.empty(Nc, dtype=torch.int32, device=dev)
         prof = torch.empty((bins, Nc), dtype=torch.float32, device=dev) if return_profile else None
         step = int(chunk_cells) if chunk_cells is not None else default_chunk_cells(Ng)
@@ -119,9 +133,7 @@ def phase_mle(counts, T, m, noisemodel="Poisson", dispersion=0.3, *, device=None
             if storage == "u16" and hi > 65535:
                 raise ValueError("storage='u16' needs every count <= 65535")
             if storage != "f32" and hi <= 65535:
-                blk = blk.to(torch.int32)
-                blk[blk >= 32768] -= 65536
-                blk = blk.to(torch.int16)                                            # the bits of the uint16 value
+                blk = u16_bits(blk)
                 kind = _lib.VC_COUNTS_U16
             else:
                 kind = _lib.VC_COUNTS_F32
