@@ -338,11 +338,25 @@ def test_header_declares_and_lib_binds_vc_gene_glm_batch():
     decl = re.search(r"\bint vc_gene_glm_batch\(([^;]*)\);", hdr).group(1)
     assert len(_lib.EXPORTS["vc_gene_glm_batch"][1]) == len(decl.split(",")) == 27
     assert decl.rstrip().endswith("void* hip_stream") and "const int64_t* seg_host" in decl
-    src = open(os.path.join(ROOT, "velocycle_amd", "csrc", "vc_gene_glm_batch.hip")).read()
-    both = [open(os.path.join(ROOT, "velocycle_amd", "csrc", f)).read() for f in ("vc_gene_glm.hip", "vc_gene_glm_batch.hip")]
-    # the per-element arithmetic is shared through the header, not copied
-    assert all('#include "vc_gene_glm_math.h"' in s and "__builtin_amdgcn_exp2f((float)(t - tn))" not in s for s in both)
-    assert "glm_sweep<H, NOISE, U16>" in both[0] and "glm_sweep<H, NOISE, U16>" in src
+    csrc = os.path.join(ROOT, "velocycle_amd", "csrc")
+    read = lambda f: open(os.path.join(csrc, f)).read()                               # noqa: E731
+    both = [read(f) for f in ("vc_gene_glm.hip", "vc_gene_glm_batch.hip")]
+    solvers = both + [read(f) for f in ("vc_gene_dispersion.hip", "vc_gene_kinetics.hip")]
+    # the per-element arithmetic, the count load and the fold are shared through the headers, not copied: by all four per-gene solvers
+    for s in solvers:
+        assert "__builtin_amdgcn_exp2f((float)(t - tn))" not in s and "__shfl_down" not in s
+        assert not re.search(r"\bfloat \w+_count\(", s) and "gene_count<U16>" in s and "gene_fold<" in s
+    assert all('#include "vc_gene_glm_math.h"' in s for s in both) and '#include "vc_gene_math.h"' in read("vc_gene_glm_math.h")
+    assert all('#include "vc_gene_math.h"' in s for s in solvers[2:])
+    assert all("glm_sweep<H, NOISE, U16>" in s for s in both)
+    # each shared statement is written once in csrc/
+    everything = "".join(read(f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
+    shared = read("vc_gene_math.h")
+    for text in ("__builtin_amdgcn_exp2f((float)(t - tn))", "float gene_count(", "void gene_fold(", "void gene_lik(", "int gene_refuse(",
+                 "int gene_fail(", "int gene_launched("):
+        assert shared.count(text) == 1 == everything.count(text), text
+    assert all("gene_exp_f32(" in s for s in (read("vc_gene_glm_math.h"), *solvers[2:]))
+    assert "gene_lik<NOISE>" in read("vc_gene_glm_math.h") and solvers[3].count("gene_lik<NOISE>") == 2
 
 
 def batch_args(**k):

@@ -315,7 +315,8 @@ def test_entry_point_validates_without_a_device():
         assert lib.vc_gene_dispersion(*disp_args(**kw)) == _lib.VC_ERR_ARG and msg in lib.vc_last_error(None), kw
     src = open(os.path.join(ROOT, "velocycle_amd", "csrc", "vc_gene_dispersion.hip")).read()
     body = src[src.index('extern "C" int vc_gene_dispersion'):]
-    assert body.rindex("dsp_fail(") < body.index("hipLaunchKernelGGL")                  # every refusal comes before the launch
+    launch = body.index("hipLaunchKernelGGL")                                            # every refusal comes before the launch
+    assert 0 < body.index("gene_refuse(") < body.index("if (refused != VC_OK) return refused;") < body.rindex("gene_fail(") < launch
 
 
 def test_the_kernel_has_no_scratch(tmp_path):

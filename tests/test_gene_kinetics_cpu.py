@@ -240,9 +240,13 @@ def test_entry_point_validates_without_a_device():
     for kw, msg in REFUSALS:
         assert lib.vc_gene_kinetics(*kin_args(**kw)) == _lib.VC_ERR_ARG and msg in lib.vc_last_error(None), kw
     assert lib.vc_gene_kinetics(*kin_args(noise=2)) == _lib.VC_ERR_UNSUPPORTED and b"Lognormal" in lib.vc_last_error(None)
-    src = open(os.path.join(ROOT, "velocycle_amd", "csrc", "vc_gene_kinetics.hip")).read()
-    body = src[src.index('extern "C" int vc_gene_kinetics'):]
-    assert body.rindex("kin_fail(") < body.index("hipLaunchKernelGGL")                  # every refusal comes before the launch
+    # in each of the four per-gene entry points the shared refusals and every refusal of its own come before the launch
+    for name in ("vc_gene_glm", "vc_gene_glm_batch", "vc_gene_dispersion", "vc_gene_kinetics"):
+        src = open(os.path.join(ROOT, "velocycle_amd", "csrc", name + ".hip")).read()
+        body = src[src.index(f'extern "C" int {name}('):]
+        launch = body.index("hipLaunchKernelGGL")
+        assert 0 < body.index("gene_refuse(") < body.index("if (refused != VC_OK) return refused;") < launch, name
+        assert body.rindex("gene_fail(") < launch < body.index("gene_launched("), name
 
 
 def test_the_kernel_has_no_scratch(tmp_path):

@@ -9,10 +9,10 @@
 //   h = d2L/dr2  = sum_c psi'(k + r) - psi'(r) + 1 / r - 1 / (r + mu) - (mu - k) / (r + mu)^2
 //   f' = r s - (alpha - 1) + beta / r,   f'' = r^2 h + r s - beta / r
 //
-// Mapping: one workgroup of DSP_NW waves per gene, lanes walk the row with stride 256 exactly as vc_gene_glm does.  mu is formed by
-// vc_gene_glm's statements (eta float64, mu = 2^n 2^f with one float32 exp2), so both kernels see the same mu; it is the only float32
-// number here.  Everything that depends on r is float64.  Sums: per-lane float64 accumulators, the shuffle tree, the waves in wave order
-// through the LDS -- no float atomics, identical bits on repetition.
+// Mapping: one workgroup of GENE_NW waves per gene, lanes walk the row with stride 256 (gene_count, as in vc_gene_glm).  mu is formed
+// as glm_sweep forms it (eta float64 by the same statements, mu = gene_exp_f32(eta): 2^n 2^f with one float32 exp2), so both kernels
+// see the same mu; it is the only float32 number here.  Everything that depends on r is float64.  Sums: per-lane float64 accumulators,
+// the shuffle tree, the waves in wave order through the LDS (gene_fold) -- no float atomics, identical bits on repetition.
 //
 // Gamma terms: counts are integers, so  sum_c psi(k + r) - psi(r) = sum_{j >= 0} N_{>j} / (r + j),  N_{>j} = #{c: k_c > j}  (lgamma: the
 // same with ln(r + j), psi': with -1 / (r + j)^2).  The first walk over the row builds the counts' histogram below DSP_T in the LDS with
@@ -30,56 +30,19 @@
 //   at rho   f'' < 0 and f'^2 / -f'' <= tol -> CONVERGED;  |f'| <= noise -> ROUNDING;  steps == max_iter -> MAX_ITER
 //   step     the sign of f' shrinks the bracket; rho' = rho - f' / f'' if f'' < 0 and rho' lies strictly inside, else the midpoint
 //   max_iter == 0: one pass at r_start -> EVALUATED.  A nu that is not finite -> NO_DATA, NaN outputs.
-#include <string>
-
-#include "vc_common.h"
-
-void vc_set_global_error(const char* msg);      // vc_engine.hip: the message vc_last_error(NULL) returns
+#include "vc_gene_math.h"                         // gene_count, gene_exp_f32, gene_fold and the entry point's refusals: shared by the per-gene solvers
 
 // every product-sum is written as the fma it is meant to be; nothing else may be contracted (the same operations in every instantiation)
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int DSP_NW = 4;                 // waves per workgroup
-constexpr int DSP_NT = DSP_NW * 64;
 constexpr int DSP_T = 1024;               // counts below it go through the histogram (why 1024)
-constexpr int DSP_PER = DSP_T / DSP_NT;   // histogram entries per lane in the scan
-constexpr double DSP_EPS32 = 1.1920928955078125e-07;
+constexpr int DSP_PER = DSP_T / GENE_NT;  // histogram entries per lane in the scan
 constexpr double DSP_EPS64 = 2.220446049250313e-16;
-constexpr double DSP_LOG2E = 1.4426950408889634;
 constexpr int DSP_L = 0, DSP_S = 1, DSP_H = 2, DSP_N = 3, DSP_P = 4, DSP_NACC = 5;
 
-template <bool U16>
-__device__ __forceinline__ float dsp_count(const void* row, long long c) {
-  if (U16) return (float)((const unsigned short*)row)[c];
-  return ((const float*)row)[c];
-}
-
-// acc[i] := the sum of acc[i] over the workgroup, in every lane: shuffle tree over the wave, then the waves in wave order
-template <int N>
-__device__ __forceinline__ void dsp_fold(double (&acc)[N], double (*part)[N], double* tot, int lane, int wave) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double v = acc[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) part[wave][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    double s = part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < DSP_NW; ++w) s += part[w][threadIdx.x];
-    tot[threadIdx.x] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) acc[i] = tot[i];
-  __syncthreads();                                                   // part / tot are written again by the next fold
-}
-
-// eta (float64) and mu (one float32 rounding) of cell c: the statements of vc_gene_glm's pass
+// eta (float64) and mu (one float32 rounding) of cell c: glm_sweep's statements and its gene_exp_f32, so that both kernels see the same mu
 template <int K>
 __device__ __forceinline__ float dsp_mu(const float* __restrict__ B, const float* __restrict__ logm, long long Nc, long long c,
                                         const double (&nu)[K], double& eta_out) {
@@ -90,11 +53,8 @@ __device__ __forceinline__ float dsp_mu(const float* __restrict__ B, const float
   double eta = (double)logm[c] + nu[0];
 #pragma unroll
   for (int i = 1; i < K; ++i) eta = __builtin_fma(nu[i], b[i], eta);
-  double t = eta * DSP_LOG2E;
-  t = t > 120.0 ? 120.0 : (t < -140.0 ? -140.0 : t);
-  const double tn = __builtin_rint(t);
   eta_out = eta;
-  return __builtin_ldexpf(__builtin_amdgcn_exp2f((float)(t - tn)), (int)tn);
+  return gene_exp_f32(eta);
 }
 
 struct DspPoint {
@@ -112,7 +72,7 @@ __device__ __forceinline__ DspPoint dsp_pass(const void* __restrict__ row, long 
   for (int i = 0; i < DSP_NACC; ++i) acc[i] = 0.0;
   const double ir = 1.0 / r;
   // the gamma terms of every count below DSP_T (and of the first DSP_T factors of the larger ones)
-  for (int j = threadIdx.x; j < DSP_T; j += DSP_NT) {
+  for (int j = threadIdx.x; j < DSP_T; j += GENE_NT) {
     const unsigned n = ngt[j];
     if (n == 0) break;
     const double x = r + (double)j, ix = 1.0 / x, nd = (double)n;
@@ -123,8 +83,8 @@ __device__ __forceinline__ DspPoint dsp_pass(const void* __restrict__ row, long 
     acc[DSP_P] += p;
   }
   const double x0 = r + (double)DSP_T, i0 = 1.0 / x0, lnx0 = log(x0);
-  for (long long c = threadIdx.x; c < Nc; c += DSP_NT) {
-    const float k = dsp_count<U16>(row, c);
+  for (long long c = threadIdx.x; c < Nc; c += GENE_NT) {
+    const float k = gene_count<U16>(row, c);
     double eta;
     const double md = (double)dsp_mu<2 * H + 1>(B, logm, Nc, c, nu, eta);
     const double kd = (double)k;
@@ -165,18 +125,19 @@ __device__ __forceinline__ DspPoint dsp_pass(const void* __restrict__ row, long 
     acc[DSP_N] = __builtin_fma(nz, nz, acc[DSP_N]);
     acc[DSP_P] += mag;
   }
-  dsp_fold<DSP_NACC>(acc, part, tot, lane, wave);
+  gene_fold<DSP_NACC>(acc, part, tot, lane, wave);
+  __syncthreads();                                                   // part / tot are written again by the next fold
   DspPoint pt;
   const double rs_ = r * acc[DSP_S];
   pt.L = acc[DSP_L];
   pt.fp = rs_ - pa + pb * ir;
   pt.fpp = __builtin_fma(r * r, acc[DSP_H], rs_) - pb * ir;
-  pt.noise = 4.0 * DSP_EPS32 * __builtin_sqrt(acc[DSP_N]) + 64.0 * DSP_EPS64 * r * acc[DSP_P];
+  pt.noise = 4.0 * GENE_EPS32 * __builtin_sqrt(acc[DSP_N]) + 64.0 * DSP_EPS64 * r * acc[DSP_P];
   return pt;
 }
 
 template <int H, bool U16>
-__global__ __launch_bounds__(DSP_NT) void vc_gene_dispersion_kernel(const void* __restrict__ counts, long long Nc, long long gene_stride,
+__global__ __launch_bounds__(GENE_NT) void vc_gene_dispersion_kernel(const void* __restrict__ counts, long long Nc, long long gene_stride,
                                                                     const float* __restrict__ B, const float* __restrict__ logm,
                                                                     const double* __restrict__ nu_in, const float* __restrict__ r_start,
                                                                     const double* __restrict__ prior_alpha,
@@ -186,10 +147,10 @@ __global__ __launch_bounds__(DSP_NT) void vc_gene_dispersion_kernel(const void* 
                                                                     double* __restrict__ score_out, int* __restrict__ iter_out,
                                                                     int* __restrict__ status_out) {
   constexpr int K = 2 * H + 1;
-  __shared__ double part[DSP_NW][DSP_NACC];
+  __shared__ double part[GENE_NW][DSP_NACC];
   __shared__ double tot[DSP_NACC];
   __shared__ unsigned ngt[DSP_T];
-  __shared__ unsigned wtot[DSP_NW];
+  __shared__ unsigned wtot[GENE_NW];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const long long g = blockIdx.x;
@@ -222,11 +183,11 @@ __global__ __launch_bounds__(DSP_NT) void vc_gene_dispersion_kernel(const void* 
   }
 
   // first walk: the histogram of the counts below DSP_T (larger ones in no bin) and the moment sums of the start
-  for (int j = threadIdx.x; j < DSP_T; j += DSP_NT) ngt[j] = 0u;
+  for (int j = threadIdx.x; j < DSP_T; j += GENE_NT) ngt[j] = 0u;
   __syncthreads();
   double mom[2] = {0.0, 0.0};
-  for (long long c = threadIdx.x; c < Nc; c += DSP_NT) {
-    const float k = dsp_count<U16>(row, c);
+  for (long long c = threadIdx.x; c < Nc; c += GENE_NT) {
+    const float k = gene_count<U16>(row, c);
     if (k >= 0.f && k < (float)DSP_T) atomicAdd(&ngt[(int)k], 1u);       // the index is inside whatever the count
     double eta;
     const double md = (double)dsp_mu<K>(B, logm, Nc, c, nu, eta);
@@ -234,7 +195,8 @@ __global__ __launch_bounds__(DSP_NT) void vc_gene_dispersion_kernel(const void* 
     mom[0] = __builtin_fma(md, md, mom[0]);
     mom[1] += __builtin_fma(dv, dv, -md);
   }
-  dsp_fold<2>(mom, (double(*)[2])(void*)&part[0][0], tot, lane, wave);
+  gene_fold<2>(mom, (double(*)[2])(void*)&part[0][0], tot, lane, wave);
+  __syncthreads();                                                   // part / tot are written again by the next fold
   // N_{>j} = Nc - #{k <= j}: every lane scans its DSP_PER consecutive bins, the lanes by a shuffle scan, the waves through the LDS
   {
     unsigned a[DSP_PER], s = 0u;
@@ -314,10 +276,7 @@ __global__ __launch_bounds__(DSP_NT) void vc_gene_dispersion_kernel(const void* 
   }
 }
 
-int dsp_fail(int code, const char* msg) {
-  vc_set_global_error(msg);
-  return code;
-}
+constexpr char DSP_FN[] = "vc_gene_dispersion";
 
 }  // namespace
 
@@ -326,18 +285,14 @@ extern "C" int vc_gene_dispersion(const void* counts_dev, int count_kind, int64_
                                   const double* prior_alpha_dev, const double* prior_beta_dev, double tol, int max_iter, double* rho_dev,
                                   float* r_dev, double* info_dev, double* loglik_dev, double* score_dev, int32_t* iterations_dev,
                                   int32_t* status_dev, void* hip_stream) {
-  if (count_kind != VC_COUNTS_F32 && count_kind != VC_COUNTS_U16) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: count_kind must be VC_COUNTS_F32 or VC_COUNTS_U16");
-  if (K != 1 && K != 3 && K != 5 && K != 7) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: K must be 1, 3, 5 or 7 (2 H + 1, H in 0..3)");
-  if (Ng < 1 || Nc < 1) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: Ng and Nc must be >= 1");
-  if (Ng > 0x7fffffffLL || Nc > 0x7fffffffLL) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: more than 2^31 - 1 genes or cells in one call");
-  if (gene_stride < Nc) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: gene_stride < Nc");
-  if (max_iter < 0) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: max_iter must be >= 0");
-  if (!(tol >= 0.0)) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: tol must be >= 0");
-  if (!counts_dev || !basis_dev || !logm_dev || !nu_dev) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: null input pointer");
-  if (!rho_dev || !r_dev || !info_dev || !loglik_dev || !score_dev || !iterations_dev || !status_dev) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: null output pointer");
-  if ((prior_alpha_dev == nullptr) != (prior_beta_dev == nullptr)) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: the prior needs both its alpha and its beta");
-  if (max_iter == 0 && !r_start_dev) return dsp_fail(VC_ERR_ARG, "vc_gene_dispersion: max_iter == 0 (evaluate only) needs r_start_dev");
-  const dim3 grid((unsigned)Ng), block(DSP_NT);
+  const int refused = gene_refuse(DSP_FN, GENE_NO_NOISE, count_kind, K != 1 && K != 3 && K != 5 && K != 7 ? "K must be 1, 3, 5 or 7 (2 H + 1, H in 0..3)" : nullptr,
+                                  Ng, Nc, true, gene_stride, 0, max_iter, tol);
+  if (refused != VC_OK) return refused;
+  if (!counts_dev || !basis_dev || !logm_dev || !nu_dev) return gene_fail(DSP_FN, VC_ERR_ARG, "null input pointer");
+  if (!rho_dev || !r_dev || !info_dev || !loglik_dev || !score_dev || !iterations_dev || !status_dev) return gene_fail(DSP_FN, VC_ERR_ARG, "null output pointer");
+  if ((prior_alpha_dev == nullptr) != (prior_beta_dev == nullptr)) return gene_fail(DSP_FN, VC_ERR_ARG, "the prior needs both its alpha and its beta");
+  if (max_iter == 0 && !r_start_dev) return gene_fail(DSP_FN, VC_ERR_ARG, "max_iter == 0 (evaluate only) needs r_start_dev");
+  const dim3 grid((unsigned)Ng), block(GENE_NT);
   hipStream_t st = (hipStream_t)hip_stream;
 #define DSP_LAUNCH(H, U16)                                                                                                             \
   hipLaunchKernelGGL((vc_gene_dispersion_kernel<H, U16>), grid, block, 0, st, counts_dev, (long long)Nc, (long long)gene_stride,       \
@@ -356,10 +311,5 @@ extern "C" int vc_gene_dispersion(const void* counts_dev, int count_kind, int64_
   }
 #undef DSP_LAUNCH_H
 #undef DSP_LAUNCH
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    try { vc_set_global_error((std::string("vc_gene_dispersion: launch failed: ") + hipGetErrorString(err)).c_str()); } catch (...) {}
-    return VC_ERR_HIP;
-  }
-  return VC_OK;
+  return gene_launched(DSP_FN);
 }

@@ -9,7 +9,7 @@
 // Gradient  sum_c res B_i,  res = k - mu | (k - mu) r / (r + mu);  observed Hessian  sum_c w B_i B_j,  w = mu | mu r (k + r) / (r + mu)^2,
 // prior precisions on its diagonal.  Both objectives are concave.
 //
-// Mapping: one workgroup of GLM_NW waves per gene, its lanes walk the gene's row of the [genes][cells] block with stride 256 (every wave
+// Mapping: one workgroup of GENE_NW waves per gene, its lanes walk the gene's row of the [genes][cells] block with stride 256 (every wave
 // instruction reads 64 consecutive cells: coalesced).  Per element: eta in float64 from the float32 tables and the float64 nu (K fmas),
 // mu = 2^n 2^f with one v_exp_f32 on the fraction (mu carries one rounding whatever |eta|), the residual, the weight and the logarithm
 // in float32.  Sums: every lane accumulates in float64 (products with B are exact there), the lanes of a wave are folded by a fixed
@@ -29,13 +29,7 @@
 //            accepted unless L' < L - 8 eps32 max(A, A') (a drop beyond the objective's own rounding), else t /= 2; a gene has
 //            GLM_MAX_HALVINGS halvings in all (then MAX_ITER): no path spins.
 // Outputs are those of the last accepted point: nu, packed H^-1, L without the prior term, dec, steps taken, status.
-#include <string>
-
-#include "vc_common.h"
-
-void vc_set_global_error(const char* msg);      // vc_engine.hip: the message vc_last_error(NULL) returns
-
-#include "vc_gene_glm_math.h"                     // the per-element arithmetic, the fold and the packed algebra, shared with vc_gene_glm_batch.hip
+#include "vc_gene_glm_math.h"                     // glm_sweep, glm_prior and the packed algebra, shared with vc_gene_glm_batch.hip; through it vc_gene_math.h
 
 #pragma clang fp contract(off)
 
@@ -50,7 +44,7 @@ __device__ __forceinline__ void glm_pass(const void* __restrict__ row, long long
 #pragma unroll
   for (int i = 0; i < S::N; ++i) acc[i] = 0.0;
   glm_sweep<H, NOISE, U16>(row, 0, Nc, Nc, B, logm, r, lnr, nu, acc);
-  glm_fold<S::N>(acc, part, tot, lane, wave);
+  gene_fold<S::N>(acc, part, tot, lane, wave);
 }
 
 // Gradient gr, Cholesky factor of the Hessian and penalty of the penalised objective at nu, from the sums of a pass
@@ -73,7 +67,7 @@ __device__ __forceinline__ bool glm_factor(const double (&acc)[GlmSums<H>::N], c
 }
 
 template <int H, int NOISE, bool U16>
-__global__ __launch_bounds__(GLM_NT) void vc_gene_glm_kernel(const void* __restrict__ counts, long long Nc, long long gene_stride,
+__global__ __launch_bounds__(GENE_NT) void vc_gene_glm_kernel(const void* __restrict__ counts, long long Nc, long long gene_stride,
                                                              const float* __restrict__ B, const float* __restrict__ logm,
                                                              const float* __restrict__ rg, const double* __restrict__ prior_mean,
                                                              const double* __restrict__ prior_prec, double tol, int max_iter,
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_kernel(const void* __restr
                                                              int* __restrict__ iter_out, int* __restrict__ status_out) {
   typedef GlmSums<H> S;
   constexpr int K = S::K, NH = S::NH;
-  __shared__ double part[GLM_NW][S::N];
+  __shared__ double part[GENE_NW][S::N];
   __shared__ double tot[S::N];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -91,27 +85,19 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_kernel(const void* __restr
   const float r = NOISE == VC_NOISE_NB ? rg[g] : 0.f;
   const double lnr = NOISE == VC_NOISE_NB ? log((double)r) : 0.0;
 
-  // the prior of this gene: a coefficient has one where its mean is finite and its precision a positive finite number
-  double pm[K], pp[K];
+  double pm[K], pp[K];                                              // the prior of this gene
 #pragma unroll
-  for (int i = 0; i < K; ++i) {
-    pm[i] = 0.0;
-    pp[i] = 0.0;
-    if (prior_mean) {
-      const double m = prior_mean[g * K + i], p = prior_prec[g * K + i];
-      if (__builtin_fabs(m) < 1.0e300 && p > 0.0 && p < 1.0e300) { pm[i] = m; pp[i] = p; }
-    }
-  }
+  for (int i = 0; i < K; ++i) glm_prior(prior_mean, prior_prec, g * K + i, pm[i], pp[i]);
 
   // start: sum k and sum e^logm
   double nu[K];
   {
     double s2[2] = {0.0, 0.0};
-    for (long long c = threadIdx.x; c < Nc; c += GLM_NT) {
-      s2[0] += (double)glm_count<U16>(row, c);
+    for (long long c = threadIdx.x; c < Nc; c += GENE_NT) {
+      s2[0] += (double)gene_count<U16>(row, c);
       s2[1] += (double)__builtin_amdgcn_exp2f(VC_LOG2E * logm[c]);
     }
-    glm_fold<2>(s2, (double(*)[2])(void*)&part[0][0], tot, lane, wave);
+    gene_fold<2>(s2, (double(*)[2])(void*)&part[0][0], tot, lane, wave);
     __syncthreads();                                               // part / tot are used with another row length below
     nu[0] = log(s2[0] / s2[1]);
 #pragma unroll
@@ -154,7 +140,7 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_kernel(const void* __restr
     if (dec <= tol) { status = VC_GLM_CONVERGED; break; }
     bool noise = true;
 #pragma unroll
-    for (int i = 0; i < K; ++i) noise = noise && __builtin_fabs(gr[i]) <= 4.0 * GLM_EPS32 * __builtin_sqrt(acc[S::OFF_N + i]);
+    for (int i = 0; i < K; ++i) noise = noise && __builtin_fabs(gr[i]) <= 4.0 * GENE_EPS32 * __builtin_sqrt(acc[S::OFF_N + i]);
     if (noise) { status = VC_GLM_ROUNDING; break; }
     if (steps >= max_iter) { status = VC_GLM_MAX_ITER; break; }
     const double Lpen = Lcur - pen;
@@ -178,7 +164,7 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_kernel(const void* __restr
         pen2 = __builtin_fma(0.5 * pp[i] * d, d, pen2);
       }
       const double A = acc[S::OFF_A] > Acur ? acc[S::OFF_A] : Acur;
-      if (acc[S::OFF_L] - pen2 >= Lpen - 8.0 * GLM_EPS32 * A) {      // false for a NaN: such a step is halved
+      if (acc[S::OFF_L] - pen2 >= Lpen - 8.0 * GENE_EPS32 * A) {      // false for a NaN: such a step is halved
 #pragma unroll
         for (int i = 0; i < K; ++i) nu[i] = trial[i];
         moved = true;
@@ -227,10 +213,7 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_kernel(const void* __restr
   }
 }
 
-int glm_fail(int code, const char* msg) {
-  vc_set_global_error(msg);
-  return code;
-}
+constexpr char GLM_FN[] = "vc_gene_glm";
 
 }  // namespace
 
@@ -238,20 +221,14 @@ extern "C" int vc_gene_glm(const void* counts_dev, int count_kind, int64_t Ng, i
                            int K, const float* logm_dev, int noise, const float* r_dev, const double* prior_mean_dev,
                            const double* prior_prec_dev, double tol, int max_iter, double* nu_dev, double* cov_dev, double* loglik_dev,
                            double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, void* hip_stream) {
-  if (noise == VC_NOISE_LOGNORMAL) return glm_fail(VC_ERR_UNSUPPORTED, "vc_gene_glm: Lognormal noise is not implemented (Poisson or NegativeBinomial)");
-  if (noise != VC_NOISE_NB && noise != VC_NOISE_POISSON) return glm_fail(VC_ERR_ARG, "vc_gene_glm: noise must be VC_NOISE_POISSON or VC_NOISE_NB");
-  if (count_kind != VC_COUNTS_F32 && count_kind != VC_COUNTS_U16) return glm_fail(VC_ERR_ARG, "vc_gene_glm: count_kind must be VC_COUNTS_F32 or VC_COUNTS_U16");
-  if (K != 1 && K != 3 && K != 5 && K != 7) return glm_fail(VC_ERR_ARG, "vc_gene_glm: K must be 1, 3, 5 or 7 (2 H + 1, H in 0..3)");
-  if (Ng < 1 || Nc < 1) return glm_fail(VC_ERR_ARG, "vc_gene_glm: Ng and Nc must be >= 1");
-  if (Ng > 0x7fffffffLL) return glm_fail(VC_ERR_ARG, "vc_gene_glm: more than 2^31 - 1 genes in one call");
-  if (gene_stride < Nc) return glm_fail(VC_ERR_ARG, "vc_gene_glm: gene_stride < Nc");
-  if (max_iter < 1) return glm_fail(VC_ERR_ARG, "vc_gene_glm: max_iter must be >= 1");
-  if (!(tol >= 0.0)) return glm_fail(VC_ERR_ARG, "vc_gene_glm: tol must be >= 0");
-  if (!counts_dev || !basis_dev || !logm_dev) return glm_fail(VC_ERR_ARG, "vc_gene_glm: null input pointer");
-  if (!nu_dev || !cov_dev || !loglik_dev || !dec_dev || !iterations_dev || !status_dev) return glm_fail(VC_ERR_ARG, "vc_gene_glm: null output pointer");
-  if (noise == VC_NOISE_NB && !r_dev) return glm_fail(VC_ERR_ARG, "vc_gene_glm: the negative binomial needs r_dev (1 / dispersion per gene)");
-  if ((prior_mean_dev == nullptr) != (prior_prec_dev == nullptr)) return glm_fail(VC_ERR_ARG, "vc_gene_glm: the prior needs both its means and its precisions");
-  const dim3 grid((unsigned)Ng), block(GLM_NT);
+  const int refused = gene_refuse(GLM_FN, noise, count_kind, K != 1 && K != 3 && K != 5 && K != 7 ? "K must be 1, 3, 5 or 7 (2 H + 1, H in 0..3)" : nullptr,
+                                  Ng, Nc, false, gene_stride, 1, max_iter, tol);
+  if (refused != VC_OK) return refused;
+  if (!counts_dev || !basis_dev || !logm_dev) return gene_fail(GLM_FN, VC_ERR_ARG, "null input pointer");
+  if (!nu_dev || !cov_dev || !loglik_dev || !dec_dev || !iterations_dev || !status_dev) return gene_fail(GLM_FN, VC_ERR_ARG, "null output pointer");
+  if (noise == VC_NOISE_NB && !r_dev) return gene_fail(GLM_FN, VC_ERR_ARG, "the negative binomial needs r_dev (1 / dispersion per gene)");
+  if ((prior_mean_dev == nullptr) != (prior_prec_dev == nullptr)) return gene_fail(GLM_FN, VC_ERR_ARG, "the prior needs both its means and its precisions");
+  const dim3 grid((unsigned)Ng), block(GENE_NT);
   hipStream_t st = (hipStream_t)hip_stream;
 #define GLM_LAUNCH(H, NOISE, U16)                                                                                                      \
   hipLaunchKernelGGL((vc_gene_glm_kernel<H, NOISE, U16>), grid, block, 0, st, counts_dev, (long long)Nc, (long long)gene_stride,       \
@@ -271,10 +248,5 @@ extern "C" int vc_gene_glm(const void* counts_dev, int count_kind, int64_t Ng, i
   }
 #undef GLM_LAUNCH_H
 #undef GLM_LAUNCH
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    try { vc_set_global_error((std::string("vc_gene_glm: launch failed: ") + hipGetErrorString(err)).c_str()); } catch (...) {}
-    return VC_ERR_HIP;
-  }
-  return VC_OK;
+  return gene_launched(GLM_FN);
 }

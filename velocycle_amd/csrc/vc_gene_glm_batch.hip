@@ -8,7 +8,7 @@
 //   minus              sum_i prec_i (nu_i - m_i)^2 / 2                 (optional, as in vc_gene_glm)
 // The objective stays concave: the offsets enter eta linearly.
 //
-// Mapping: vc_gene_glm's (vc_gene_glm_math.h: the same statements per element, the same fold).  A pass walks the segments one after the
+// Mapping: vc_gene_glm's (glm_sweep of vc_gene_glm_math.h per element, gene_fold of vc_gene_math.h).  A pass walks the segments one after the
 // other with nu_0 + delta_b for nu_0 and folds after each; the sums of a segment are those of a whole pass of vc_gene_glm, and because
 // b_0 = 1 their column 0 is the delta block:  sum res = dL/d delta_b,  sum w B_i = h_b (the cross column; h_b0 = W_b = sum w),
 // N[0] the rounding scale of dL/d delta_b.  Thread 0 adds the segment to the gene's totals in the LDS (segments in order: fixed bits) and
@@ -24,13 +24,7 @@
 // SINGULAR when a D_b or a pivot of S is not a positive finite number (a q_b or m_b that is not: the same); CONVERGED on dec <= tol;
 // ROUNDING when every one of the K + Nb gradient entries is within 4 eps32 sqrt(N_i); MAX_ITER; the full step halved on the penalised
 // objective (30 halvings per gene); UNBOUNDED when a harmonic or a delta_b of a trial leaves [-50, 50], or the gene has no count.
-#include <string>
-
-#include "vc_common.h"
-
-void vc_set_global_error(const char* msg);      // vc_engine.hip: the message vc_last_error(NULL) returns
-
-#include "vc_gene_glm_math.h"
+#include "vc_gene_glm_math.h"                     // glm_sweep, glm_prior and the packed algebra, shared with vc_gene_glm.hip; through it vc_gene_math.h
 
 #pragma clang fp contract(off)
 
@@ -79,7 +73,7 @@ __device__ __forceinline__ void glmb_pass(const void* __restrict__ row, long lon
 #pragma unroll
     for (int i = 0; i < S::N; ++i) acc[i] = 0.0;
     glm_sweep<H, NOISE, U16>(row, seg.s[b], seg.s[b + 1], Nc, B, logm, r, lnr, nub, acc);
-    glm_fold<S::N>(acc, part, tot, lane, wave);
+    gene_fold<S::N>(acc, part, tot, lane, wave);
     if (threadIdx.x == 0) {
 #pragma unroll
       for (int i = 0; i < S::N; ++i) gsum[i] = b == 0 ? acc[i] : gsum[i] + acc[i];
@@ -128,7 +122,7 @@ __device__ __forceinline__ bool glmb_factor(const double (&acc)[GlmSums<H>::N], 
     pen = __builtin_fma(0.5 * q * dm, dm, pen);
     rhs[0] = __builtin_fma(q, __builtin_fma(gb, iD, dm), rhs[0]);
     gd2 = __builtin_fma(gb * iD, gb, gd2);
-    delta_noise = delta_noise && __builtin_fabs(gb) <= 4.0 * GLM_EPS32 * __builtin_sqrt(s.n0[b]);
+    delta_noise = delta_noise && __builtin_fabs(gb) <= 4.0 * GENE_EPS32 * __builtin_sqrt(s.n0[b]);
 #pragma unroll
     for (int i = 0; i < K; ++i) {
       const double hi = s.h[b][i];
@@ -145,7 +139,7 @@ __device__ __forceinline__ bool glmb_factor(const double (&acc)[GlmSums<H>::N], 
 }
 
 template <int H, int NOISE, bool U16>
-__global__ __launch_bounds__(GLM_NT) void vc_gene_glm_batch_kernel(
+__global__ __launch_bounds__(GENE_NT) void vc_gene_glm_batch_kernel(
     const void* __restrict__ counts, long long Nc, long long gene_stride, const float* __restrict__ B, const float* __restrict__ logm,
     const float* __restrict__ rg, int Nb, const GlmSeg seg, const double* __restrict__ delta_mean, const double* __restrict__ delta_prec,
     const double* __restrict__ prior_mean, const double* __restrict__ prior_prec, double tol, int max_iter, double* __restrict__ nu_out,
@@ -153,7 +147,7 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_batch_kernel(
     double* __restrict__ dec_out, int* __restrict__ iter_out, int* __restrict__ status_out) {
   typedef GlmSums<H> S;
   constexpr int K = S::K, NH = S::NH;
-  __shared__ double part[GLM_NW][S::N];
+  __shared__ double part[GENE_NW][S::N];
   __shared__ double tot[S::N];
   __shared__ double gsum[S::N];
   __shared__ GlmbLds<K> s;
@@ -166,16 +160,9 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_batch_kernel(
   const double lnr = NOISE == VC_NOISE_NB ? log((double)r) : 0.0;
   const double nan = __builtin_nan("");
 
-  double pm[K], pp[K];
+  double pm[K], pp[K];                                              // the prior of nu
 #pragma unroll
-  for (int i = 0; i < K; ++i) {
-    pm[i] = 0.0;
-    pp[i] = 0.0;
-    if (prior_mean) {
-      const double m = prior_mean[g * K + i], p = prior_prec[g * K + i];
-      if (__builtin_fabs(m) < 1.0e300 && p > 0.0 && p < 1.0e300) { pm[i] = m; pp[i] = p; }
-    }
-  }
+  for (int i = 0; i < K; ++i) glm_prior(prior_mean, prior_prec, g * K + i, pm[i], pp[i]);
   if (tb < Nb) {
     const double m = delta_mean[g * Nb + tb];
     s.m[tb] = m;
@@ -189,11 +176,11 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_batch_kernel(
   double nu[K];
   {
     double s2[2] = {0.0, 0.0};
-    for (long long c = threadIdx.x; c < Nc; c += GLM_NT) {
-      s2[0] += (double)glm_count<U16>(row, c);
+    for (long long c = threadIdx.x; c < Nc; c += GENE_NT) {
+      s2[0] += (double)gene_count<U16>(row, c);
       s2[1] += (double)__builtin_amdgcn_exp2f(VC_LOG2E * logm[c]);
     }
-    glm_fold<2>(s2, (double(*)[2])(void*)&part[0][0], tot, lane, wave);
+    gene_fold<2>(s2, (double(*)[2])(void*)&part[0][0], tot, lane, wave);
     __syncthreads();                                               // part / tot are used with another row length below
     nu[0] = log(s2[0] / s2[1]);
 #pragma unroll
@@ -240,7 +227,7 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_batch_kernel(
     if (dec <= tol) { status = VC_GLM_CONVERGED; break; }
     bool noise = delta_noise;
 #pragma unroll
-    for (int i = 0; i < K; ++i) noise = noise && __builtin_fabs(gr[i]) <= 4.0 * GLM_EPS32 * __builtin_sqrt(acc[S::OFF_N + i]);
+    for (int i = 0; i < K; ++i) noise = noise && __builtin_fabs(gr[i]) <= 4.0 * GENE_EPS32 * __builtin_sqrt(acc[S::OFF_N + i]);
     if (noise) { status = VC_GLM_ROUNDING; break; }
     if (steps >= max_iter) { status = VC_GLM_MAX_ITER; break; }
     if (tb < Nb) {
@@ -282,7 +269,7 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_batch_kernel(
       glmb_pass<H, NOISE, U16>(row, Nc, B, logm, r, lnr, trial, Nb, seg, s, gsum, acc, part, tot, lane, wave);
       overwritten = true;
       const double A = acc[S::OFF_A] > Acur ? acc[S::OFF_A] : Acur;
-      if (acc[S::OFF_L] - pen2 >= Lpen - 8.0 * GLM_EPS32 * A) {      // false for a NaN: such a step is halved
+      if (acc[S::OFF_L] - pen2 >= Lpen - 8.0 * GENE_EPS32 * A) {      // false for a NaN: such a step is halved
 #pragma unroll
         for (int i = 0; i < K; ++i) nu[i] = trial[i];
         if (tb < Nb) s.delta[tb] = s.trial[tb];
@@ -352,10 +339,7 @@ __global__ __launch_bounds__(GLM_NT) void vc_gene_glm_batch_kernel(
   }
 }
 
-int glmb_fail(int code, const char* msg) {
-  vc_set_global_error(msg);
-  return code;
-}
+constexpr char GLMB_FN[] = "vc_gene_glm_batch";
 
 }  // namespace
 
@@ -365,31 +349,25 @@ extern "C" int vc_gene_glm_batch(const void* counts_dev, int count_kind, int64_t
                                  const double* prior_prec_dev, double tol, int max_iter, double* nu_dev, double* delta_dev, double* cov_nu_dev,
                                  double* delta_var_dev, double* loglik_dev, double* dec_dev, int32_t* iterations_dev, int32_t* status_dev,
                                  void* hip_stream) {
-  if (noise == VC_NOISE_LOGNORMAL) return glmb_fail(VC_ERR_UNSUPPORTED, "vc_gene_glm_batch: Lognormal noise is not implemented (Poisson or NegativeBinomial)");
-  if (noise != VC_NOISE_NB && noise != VC_NOISE_POISSON) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: noise must be VC_NOISE_POISSON or VC_NOISE_NB");
-  if (count_kind != VC_COUNTS_F32 && count_kind != VC_COUNTS_U16) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: count_kind must be VC_COUNTS_F32 or VC_COUNTS_U16");
-  if (K != 1 && K != 3 && K != 5 && K != 7) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: K must be 1, 3, 5 or 7 (2 H + 1, H in 0..3)");
-  if (Ng < 1 || Nc < 1) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: Ng and Nc must be >= 1");
-  if (Ng > 0x7fffffffLL) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: more than 2^31 - 1 genes in one call");
-  if (gene_stride < Nc) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: gene_stride < Nc");
-  if (max_iter < 1) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: max_iter must be >= 1");
-  if (!(tol >= 0.0)) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: tol must be >= 0");
-  if (Nb < 1 || Nb > VC_GLM_MAX_BATCHES) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: Nb must be in 1..VC_GLM_MAX_BATCHES");
-  if (!counts_dev || !basis_dev || !logm_dev || !seg_host) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: null input pointer");
+  const int refused = gene_refuse(GLMB_FN, noise, count_kind, K != 1 && K != 3 && K != 5 && K != 7 ? "K must be 1, 3, 5 or 7 (2 H + 1, H in 0..3)" : nullptr,
+                                  Ng, Nc, false, gene_stride, 1, max_iter, tol);
+  if (refused != VC_OK) return refused;
+  if (Nb < 1 || Nb > VC_GLM_MAX_BATCHES) return gene_fail(GLMB_FN, VC_ERR_ARG, "Nb must be in 1..VC_GLM_MAX_BATCHES");
+  if (!counts_dev || !basis_dev || !logm_dev || !seg_host) return gene_fail(GLMB_FN, VC_ERR_ARG, "null input pointer");
   if (!delta_prior_mean_dev || !delta_prior_prec_dev)
-    return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: every batch offset needs its prior (delta_prior_mean_dev, delta_prior_prec_dev)");
+    return gene_fail(GLMB_FN, VC_ERR_ARG, "every batch offset needs its prior (delta_prior_mean_dev, delta_prior_prec_dev)");
   if (!nu_dev || !delta_dev || !cov_nu_dev || !delta_var_dev || !loglik_dev || !dec_dev || !iterations_dev || !status_dev)
-    return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: null output pointer");
-  if (noise == VC_NOISE_NB && !r_dev) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: the negative binomial needs r_dev (1 / dispersion per gene)");
-  if ((prior_mean_dev == nullptr) != (prior_prec_dev == nullptr)) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: the prior of nu needs both its means and its precisions");
+    return gene_fail(GLMB_FN, VC_ERR_ARG, "null output pointer");
+  if (noise == VC_NOISE_NB && !r_dev) return gene_fail(GLMB_FN, VC_ERR_ARG, "the negative binomial needs r_dev (1 / dispersion per gene)");
+  if ((prior_mean_dev == nullptr) != (prior_prec_dev == nullptr)) return gene_fail(GLMB_FN, VC_ERR_ARG, "the prior of nu needs both its means and its precisions");
   GlmSeg seg;
   for (int b = 0; b <= VC_GLM_MAX_BATCHES; ++b) seg.s[b] = b <= Nb ? (long long)seg_host[b] : (long long)Nc;
-  if (seg.s[0] != 0 || seg.s[Nb] != (long long)Nc) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: seg must start at 0 and end at Nc");
+  if (seg.s[0] != 0 || seg.s[Nb] != (long long)Nc) return gene_fail(GLMB_FN, VC_ERR_ARG, "seg must start at 0 and end at Nc");
   for (int b = 0; b < Nb; ++b) {
-    if (seg.s[b + 1] < seg.s[b]) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: seg must be non-decreasing");
-    if (seg.s[b + 1] == seg.s[b]) return glmb_fail(VC_ERR_ARG, "vc_gene_glm_batch: empty segment (a batch without a cell)");
+    if (seg.s[b + 1] < seg.s[b]) return gene_fail(GLMB_FN, VC_ERR_ARG, "seg must be non-decreasing");
+    if (seg.s[b + 1] == seg.s[b]) return gene_fail(GLMB_FN, VC_ERR_ARG, "empty segment (a batch without a cell)");
   }
-  const dim3 grid((unsigned)Ng), block(GLM_NT);
+  const dim3 grid((unsigned)Ng), block(GENE_NT);
   hipStream_t st = (hipStream_t)hip_stream;
 #define GLMB_LAUNCH(H, NOISE, U16)                                                                                                     \
   hipLaunchKernelGGL((vc_gene_glm_batch_kernel<H, NOISE, U16>), grid, block, 0, st, counts_dev, (long long)Nc, (long long)gene_stride, \
@@ -410,10 +388,5 @@ extern "C" int vc_gene_glm_batch(const void* counts_dev, int count_kind, int64_t
   }
 #undef GLMB_LAUNCH_H
 #undef GLMB_LAUNCH
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    try { vc_set_global_error((std::string("vc_gene_glm_batch: launch failed: ") + hipGetErrorString(err)).c_str()); } catch (...) {}
-    return VC_ERR_HIP;
-  }
-  return VC_OK;
+  return gene_launched(GLMB_FN);
 }

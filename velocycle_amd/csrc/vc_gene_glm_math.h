@@ -1,50 +1,19 @@
-// What vc_gene_glm.hip and vc_gene_glm_batch.hip share, statement for statement: the per-element arithmetic of the harmonic regression
-// (eta in float64 from the float32 tables, mu = 2^n 2^f with one v_exp_f32, residual, weight and NB logarithm in float32, float64
-// per-lane sums), the fold of the workgroup (shuffle tree, waves in wave order through the LDS) and the packed float64 Cholesky algebra.
-// The contract of every piece is the one written at the head of vc_gene_glm.hip.
+// What vc_gene_glm.hip and vc_gene_glm_batch.hip share, statement for statement, beyond what every per-gene solver shares
+// (vc_gene_math.h: the count load, mu = 2^n 2^f, the likelihood element, the fold): the sums of the harmonic regression per element
+// (eta in float64 from the float32 tables, float64 per-lane sums of the float32 residual and weight against the float64 basis row),
+// the prior of a coefficient and the packed float64 Cholesky algebra.  The contract of every piece is the one written at the head
+// of vc_gene_glm.hip.
 #pragma once
 
-#include "vc_common.h"
+#include "vc_gene_math.h"
 
 // every product-sum is written as the fma it is meant to be; nothing else may be contracted (the same operations in every instantiation)
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int GLM_NW = 4;                 // waves per workgroup
-constexpr int GLM_NT = GLM_NW * 64;
 constexpr int GLM_MAX_HALVINGS = 30;
-constexpr double GLM_EPS32 = 1.1920928955078125e-07;
-constexpr double GLM_LOG2E = 1.4426950408889634;
 constexpr double GLM_BOUND = 50.0;
-
-template <bool U16>
-__device__ __forceinline__ float glm_count(const void* row, long long c) {
-  if (U16) return (float)((const unsigned short*)row)[c];
-  return ((const float*)row)[c];
-}
-
-// acc[i] := the sum of acc[i] over the workgroup, in every lane: shuffle tree over the wave, then the waves in wave order
-template <int N>
-__device__ __forceinline__ void glm_fold(double (&acc)[N], double (*part)[N], double* tot, int lane, int wave) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double v = acc[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) part[wave][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    double s = part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < GLM_NW; ++w) s += part[w][threadIdx.x];
-    tot[threadIdx.x] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) acc[i] = tot[i];
-}
 
 // index of (i, j), j <= i, in the packed lower triangle
 __device__ __host__ constexpr int glm_tri(int i, int j) { return i * (i + 1) / 2 + j; }
@@ -64,8 +33,8 @@ __device__ __forceinline__ void glm_sweep(const void* __restrict__ row, long lon
                                           const double (&nu)[2 * H + 1], double (&acc)[GlmSums<H>::N]) {
   typedef GlmSums<H> S;
   constexpr int K = S::K;
-  for (long long c = c0 + threadIdx.x; c < c1; c += GLM_NT) {
-    const float k = glm_count<U16>(row, c);
+  for (long long c = c0 + threadIdx.x; c < c1; c += GENE_NT) {
+    const float k = gene_count<U16>(row, c);
     double b[K];
     b[0] = 1.0;
 #pragma unroll
@@ -73,38 +42,10 @@ __device__ __forceinline__ void glm_sweep(const void* __restrict__ row, long lon
     double eta = (double)logm[c] + nu[0];
 #pragma unroll
     for (int i = 1; i < K; ++i) eta = __builtin_fma(nu[i], b[i], eta);
-    // mu = 2^n 2^f: the fraction is exact in float64 and rounds once to float32; beyond 2^120 the step is refused by its objective
-    double t = eta * GLM_LOG2E;
-    t = t > 120.0 ? 120.0 : (t < -140.0 ? -140.0 : t);
-    const double tn = __builtin_rint(t);
-    const float mu = __builtin_ldexpf(__builtin_amdgcn_exp2f((float)(t - tn)), (int)tn);
-    const double kd = (double)k;
-    float res, w;
+    const float mu = gene_exp_f32(eta);
+    float res, wf, w;                                               // the Hessian is the observed one: the Fisher weight wf is not used
     double term, mag;
-    if (NOISE == VC_NOISE_NB) {
-      const float s = r + mu;
-      const float rs = __builtin_amdgcn_rcpf(s);
-      const float p = r * rs;                                       // r / (r + mu)
-      res = (k - mu) * p;
-      w = (mu * rs) * p * (k + r);
-      // ln(r + mu) = max(eta, ln r) + ln(1 + x), x = min(mu, r) / max(mu, r): the large part is exact in float64, the float32
-      // logarithm is taken of a number in [1, 2], so d and w lose nothing to the size of eta (counts of 10^4: (k + r) ln(r + mu) ~ 10^5)
-      const bool big = mu >= r;
-      const float x = (big ? r : mu) * __builtin_amdgcn_rcpf(big ? mu : r);
-      const double lg = (double)(VC_LN2 * __builtin_amdgcn_logf(1.f + x));
-      const double e = eta - lnr;
-      const double d = big ? -lg : e - lg;                          // eta - ln(r + mu)
-      const double wl = big ? e + lg : lg;                          // ln(r + mu) - ln r
-      const double ls = (big ? eta : lnr) + lg;
-      const double kr = (double)(k + r);
-      term = __builtin_fma(kd, d, -(double)r * wl);
-      mag = __builtin_fma(kr, __builtin_fabs(ls), __builtin_fabs(kd * eta));
-    } else {
-      res = k - mu;
-      w = mu;
-      term = __builtin_fma(kd, eta, -(double)mu);
-      mag = __builtin_fabs(kd * eta) + (double)mu;
-    }
+    gene_lik<NOISE>(k, mu, eta, r, lnr, res, wf, w, term, mag);
     const double rd = (double)res, wd = (double)w;
     const double n2 = __builtin_fma(wd, wd, rd * rd);
 #pragma unroll
@@ -160,6 +101,16 @@ __device__ __forceinline__ void glm_solve(const double (&l)[K * (K + 1) / 2], do
 #pragma unroll
     for (int q = i + 1; q < K; ++q) s = __builtin_fma(-l[glm_tri(q, i)], x[q], s);
     x[i] = s / l[glm_tri(i, i)];
+  }
+}
+
+// The prior of one coefficient (at = g K + i): it has one where its mean is finite and its precision a positive finite number
+__device__ __forceinline__ void glm_prior(const double* prior_mean, const double* prior_prec, long long at, double& pm, double& pp) {
+  pm = 0.0;
+  pp = 0.0;
+  if (prior_mean) {
+    const double m = prior_mean[at], p = prior_prec[at];
+    if (__builtin_fabs(m) < 1.0e300 && p > 0.0 && p < 1.0e300) { pm = m; pp = p; }
   }
 }
 

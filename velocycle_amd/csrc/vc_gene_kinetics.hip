@@ -14,12 +14,12 @@
 // Derivatives of etaU: p = a e^x / zp (x), -1 (y), q W_i with q = a d / zp (nuw_i); d2 etaU / dx2 = p (1 - p).  Residual and weights:
 //   res = k - mu | (k - mu) r / (r + mu)     w (Fisher) = mu | mu r / (r + mu)     wo (observed) = mu | mu r (k + r) / (r + mu)^2
 //
-// Mapping: one workgroup of KIN_NW waves per gene, lanes walk the row with stride 256 exactly as vc_gene_glm does.  etaS, d, om, z and
-// etaS - y are float64 from the float32 tables and the float64 parameters (the set of clamped cells is that of a float64 evaluation of
-// the tables); e^(etaS - y) = 2^n 2^f with one float32 exp2 (vc_gene_glm's statements), mu is its float32 product with zp; res, w, wo
-// and the NB logarithm are float32 as in glm_pass, ln zp is a float32 logarithm.  Sums: per-lane float64 accumulators, the shuffle
-// tree, the waves in wave order through the LDS -- no atomics, identical bits on repetition.  After the fold every lane holds the same
-// totals and runs the same 2 x 2 float64 algebra: the control flow is uniform.
+// Mapping: one workgroup of GENE_NW waves per gene, lanes walk the row with stride 256 (gene_count, as in vc_gene_glm).  etaS, d, om, z
+// and etaS - y are float64 from the float32 tables and the float64 parameters (the set of clamped cells is that of a float64 evaluation
+// of the tables); e^(etaS - y) = 2^n 2^f with one float32 exp2 (gene_exp_f32), mu is its float32 product with zp; res, w, wo and the
+// NB logarithm are float32 (gene_lik, the element of glm_sweep, with etaU for eta), ln zp is a float32 logarithm.  Sums: per-lane
+// float64 accumulators, the shuffle tree, the waves in wave order through the LDS (gene_fold) -- no atomics, identical bits on
+// repetition.  After the fold every lane holds the same totals and runs the same 2 x 2 float64 algebra: the control flow is uniform.
 //
 // Iteration over (x, y) in [-30, 30]^2 (status codes: velocycle_hip.h):
 //   start    start_dev, or x = mx, y = ln(sum_c e^etaS zp / sum_c k) (clipped to the box)
@@ -34,57 +34,20 @@
 //   max_iter == 0: one pass at start_dev -> EVALUATED.  A coefficient, a prior or r that is not finite, or no count -> NO_DATA, NaN.
 // With NW > 0 one more pass at the returned point forms the score of nuw and its profile information (the Fisher information of nuw
 // with (x, y) profiled out under their priors).
-#include <string>
-
-#include "vc_common.h"
-
-void vc_set_global_error(const char* msg);      // vc_engine.hip: the message vc_last_error(NULL) returns
+#include "vc_gene_math.h"                         // gene_count, gene_exp_f32, gene_lik, gene_fold and the entry point's refusals: shared by the per-gene solvers
 
 // every product-sum is written as the fma it is meant to be; nothing else may be contracted (the same operations in every instantiation)
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int KIN_NW = 4;                 // waves per workgroup
-constexpr int KIN_NT = KIN_NW * 64;
 constexpr int KIN_MAX_HALVINGS = 30;
-constexpr double KIN_EPS32 = 1.1920928955078125e-07;
-constexpr double KIN_LOG2E = 1.4426950408889634;
 constexpr double KIN_BOUND = 30.0;
 constexpr double KIN_FLOOR = 1.0e-5;      // the model's relu(z) + 1e-5
 // sums of a pass: gradient, Fisher matrix, observed matrix, rounding scales of the gradient, objective, sum |terms|, clamped cells
 constexpr int KIN_GX = 0, KIN_GY = 1, KIN_FXX = 2, KIN_FXY = 3, KIN_FYY = 4, KIN_OXX = 5, KIN_OXY = 6, KIN_OYY = 7, KIN_NX = 8,
               KIN_NY = 9, KIN_L = 10, KIN_A = 11, KIN_C = 12, KIN_NACC = 13;
 constexpr int KIN_NLDS = 18;              // the longest row folded: the profile pass at NW = 3
-
-template <bool U16>
-__device__ __forceinline__ float kin_count(const void* row, long long c) {
-  if (U16) return (float)((const unsigned short*)row)[c];
-  return ((const float*)row)[c];
-}
-
-// acc[i] := the sum of acc[i] over the workgroup, in every lane: shuffle tree over the wave, then the waves in wave order
-template <int N>
-__device__ __forceinline__ void kin_fold(double (&acc)[N], double (*part)[KIN_NLDS], double* tot, int lane, int wave) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double v = acc[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) part[wave][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    double s = part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < KIN_NW; ++w) s += part[w][threadIdx.x];
-    tot[threadIdx.x] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) acc[i] = tot[i];
-  __syncthreads();                                                   // part / tot are written again by the next fold
-}
 
 // The parameters of a gene that every pass reads
 template <int H, int NW>
@@ -135,43 +98,8 @@ __device__ __forceinline__ KinCell kin_cell(const float* __restrict__ B, const f
   o.zp = o.a ? z + KIN_FLOOR : KIN_FLOOR;
   o.d = d;
   o.e0 = eta - y;
-  // e^(etaS - y) = 2^n 2^f: the fraction is exact in float64 and rounds once to float32 (vc_gene_glm's statements)
-  double t = o.e0 * KIN_LOG2E;
-  t = t > 120.0 ? 120.0 : (t < -140.0 ? -140.0 : t);
-  const double tn = __builtin_rint(t);
-  o.m0 = __builtin_ldexpf(__builtin_amdgcn_exp2f((float)(t - tn)), (int)tn);
+  o.m0 = gene_exp_f32(o.e0);
   return o;
-}
-
-// res, the Fisher weight w, the observed weight wo, the term of the objective and its magnitude: glm_pass with etaU for eta
-template <int NOISE>
-__device__ __forceinline__ void kin_lik(float k, float mu, double etaU, float r, double lnr, float& res, float& w, float& wo, double& term,
-                                        double& mag) {
-  const double kd = (double)k;
-  if (NOISE == VC_NOISE_NB) {
-    const float s = r + mu;
-    const float rs = __builtin_amdgcn_rcpf(s);
-    const float p = r * rs;                                         // r / (r + mu)
-    res = (k - mu) * p;
-    w = mu * p;
-    wo = (mu * rs) * p * (k + r);
-    const bool big = mu >= r;
-    const float x = (big ? r : mu) * __builtin_amdgcn_rcpf(big ? mu : r);
-    const double lg = (double)(VC_LN2 * __builtin_amdgcn_logf(1.f + x));
-    const double e = etaU - lnr;
-    const double dd = big ? -lg : e - lg;                           // etaU - ln(r + mu)
-    const double wl = big ? e + lg : lg;                            // ln(r + mu) - ln r
-    const double ls = (big ? etaU : lnr) + lg;
-    const double kr = (double)(k + r);
-    term = __builtin_fma(kd, dd, -(double)r * wl);
-    mag = __builtin_fma(kr, __builtin_fabs(ls), __builtin_fabs(kd * etaU));
-  } else {
-    res = k - mu;
-    w = mu;
-    wo = mu;
-    term = __builtin_fma(kd, etaU, -(double)mu);
-    mag = __builtin_fabs(kd * etaU) + (double)mu;
-  }
 }
 
 // One pass over the gene's cells at (x, y): the KIN_NACC sums, folded over the workgroup
@@ -182,8 +110,8 @@ __device__ __forceinline__ void kin_pass(const void* __restrict__ row, long long
 #pragma unroll
   for (int i = 0; i < KIN_NACC; ++i) acc[i] = 0.0;
   const double ex = exp(x);
-  for (long long c = threadIdx.x; c < Nc; c += KIN_NT) {
-    const float k = kin_count<U16>(row, c);
+  for (long long c = threadIdx.x; c < Nc; c += GENE_NT) {
+    const float k = gene_count<U16>(row, c);
     double wr[KinGene<H, NW>::NWA];
     const KinCell cl = kin_cell<H, NW>(B, logm, W, Nc, c, G, ex, y, wr);
     const float zpf = (float)cl.zp;
@@ -191,7 +119,7 @@ __device__ __forceinline__ void kin_pass(const void* __restrict__ row, long long
     const double etaU = cl.e0 + (double)(VC_LN2 * __builtin_amdgcn_logf(zpf));
     float res, w, wo;
     double term, mag;
-    kin_lik<NOISE>(k, mu, etaU, G.r, G.lnr, res, w, wo, term, mag);
+    gene_lik<NOISE>(k, mu, etaU, G.r, G.lnr, res, w, wo, term, mag);
     const double p = cl.a ? ex / cl.zp : 0.0;
     const double rd = (double)res, wd = (double)w, od = (double)wo;
     const double n2 = __builtin_fma(od, od, rd * rd);
@@ -211,7 +139,8 @@ __device__ __forceinline__ void kin_pass(const void* __restrict__ row, long long
     acc[KIN_A] += mag;
     acc[KIN_C] += cl.a ? 0.0 : 1.0;
   }
-  kin_fold<KIN_NACC>(acc, part, tot, lane, wave);
+  gene_fold<KIN_NACC>(acc, part, tot, lane, wave);
+  __syncthreads();                                                   // part / tot are written again by the next fold
 }
 
 // The point's gradient G, the matrix A its step is taken with (observed where positive definite, else Fisher; priors included), A^-1
@@ -257,13 +186,12 @@ __device__ __forceinline__ void kin_profile(const void* __restrict__ row, long l
                                             double (*part)[KIN_NLDS], double* tot, int lane, int wave) {
   constexpr int NWA = KinGene<H, NW>::NWA, NH = NWA * (NWA + 1) / 2;
   constexpr int OS = 0, OI = NWA, OX = OI + NH, OY = OX + NWA, OF = OY + NWA, N = OF + 3;
-  static_assert(N <= KIN_NLDS, "the LDS rows are too short");
   double acc[N];
 #pragma unroll
   for (int i = 0; i < N; ++i) acc[i] = 0.0;
   const double ex = exp(x);
-  for (long long c = threadIdx.x; c < Nc; c += KIN_NT) {
-    const float k = kin_count<U16>(row, c);
+  for (long long c = threadIdx.x; c < Nc; c += GENE_NT) {
+    const float k = gene_count<U16>(row, c);
     double wr[NWA];
     const KinCell cl = kin_cell<H, NW>(B, logm, W, Nc, c, G, ex, y, wr);
     const float zpf = (float)cl.zp;
@@ -271,7 +199,7 @@ __device__ __forceinline__ void kin_profile(const void* __restrict__ row, long l
     const double etaU = cl.e0 + (double)(VC_LN2 * __builtin_amdgcn_logf(zpf));
     float res, w, wo;
     double term, mag;
-    kin_lik<NOISE>(k, mu, etaU, G.r, G.lnr, res, w, wo, term, mag);
+    gene_lik<NOISE>(k, mu, etaU, G.r, G.lnr, res, w, wo, term, mag);
     const double izp = 1.0 / cl.zp;
     const double p = cl.a ? ex * izp : 0.0, q = cl.a ? cl.d * izp : 0.0;
     const double rd = (double)res, wd = (double)w;
@@ -289,7 +217,8 @@ __device__ __forceinline__ void kin_profile(const void* __restrict__ row, long l
     acc[OF + 1] -= wp;
     acc[OF + 2] += wd;
   }
-  kin_fold<N>(acc, part, tot, lane, wave);
+  gene_fold<N>(acc, part, tot, lane, wave);
+  __syncthreads();                                                   // part / tot are written again by the next fold
   const double a = acc[OF + 0] + px, b = acc[OF + 1], cc = acc[OF + 2] + py;
   const double id = 1.0 / __builtin_fma(a, cc, -b * b);
   const double ixx = cc * id, ixy = -b * id, iyy = a * id;
@@ -305,7 +234,7 @@ __device__ __forceinline__ void kin_profile(const void* __restrict__ row, long l
 }
 
 template <int H, int NW, int NOISE, bool U16>
-__global__ __launch_bounds__(KIN_NT) void vc_gene_kinetics_kernel(const void* __restrict__ counts, long long Nc, long long gene_stride,
+__global__ __launch_bounds__(GENE_NT) void vc_gene_kinetics_kernel(const void* __restrict__ counts, long long Nc, long long gene_stride,
                                                                   const float* __restrict__ B, const float* __restrict__ logm,
                                                                   const double* __restrict__ nu_in, const float* __restrict__ W,
                                                                   const double* __restrict__ nuw_in, const float* __restrict__ rg,
@@ -317,7 +246,7 @@ __global__ __launch_bounds__(KIN_NT) void vc_gene_kinetics_kernel(const void* __
                                                                   double* __restrict__ score_out, double* __restrict__ info_out) {
   typedef KinGene<H, NW> GT;
   constexpr int K = GT::K, NWA = GT::NWA, NWH = NWA * (NWA + 1) / 2;
-  __shared__ double part[KIN_NW][KIN_NLDS];
+  __shared__ double part[GENE_NW][KIN_NLDS];
   __shared__ double tot[KIN_NLDS];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -357,13 +286,14 @@ __global__ __launch_bounds__(KIN_NT) void vc_gene_kinetics_kernel(const void* __
   if (finite) {
     double s2[2] = {0.0, 0.0};
     const double ex = exp(mx);
-    for (long long c = threadIdx.x; c < Nc; c += KIN_NT) {
+    for (long long c = threadIdx.x; c < Nc; c += GENE_NT) {
       double wr[NWA];
       const KinCell cl = kin_cell<H, NW>(B, logm, W, Nc, c, G, ex, 0.0, wr);
-      s2[0] += (double)kin_count<U16>(row, c);
+      s2[0] += (double)gene_count<U16>(row, c);
       s2[1] = __builtin_fma((double)cl.m0, cl.zp, s2[1]);
     }
-    kin_fold<2>(s2, part, tot, lane, wave);
+    gene_fold<2>(s2, part, tot, lane, wave);
+    __syncthreads();                                                 // part / tot are written again by the next fold
     y = log(s2[1] / s2[0]);
     finite = s2[0] > 0.0 && __builtin_fabs(y) < 1.0e300;
     if (start) {
@@ -405,8 +335,8 @@ __global__ __launch_bounds__(KIN_NT) void vc_gene_kinetics_kernel(const void* __
     if (max_iter == 0) { status = VC_KIN_EVALUATED; break; }
     if (!(__builtin_fabs(st.dec) < 1.0e300)) { status = VC_KIN_MAX_ITER; break; }
     if (st.dec <= tol) { status = VC_KIN_CONVERGED; break; }
-    if (__builtin_fabs(st.gx) <= 4.0 * KIN_EPS32 * __builtin_sqrt(acc[KIN_NX]) &&
-        __builtin_fabs(st.gy) <= 4.0 * KIN_EPS32 * __builtin_sqrt(acc[KIN_NY])) { status = VC_KIN_ROUNDING; break; }
+    if (__builtin_fabs(st.gx) <= 4.0 * GENE_EPS32 * __builtin_sqrt(acc[KIN_NX]) &&
+        __builtin_fabs(st.gy) <= 4.0 * GENE_EPS32 * __builtin_sqrt(acc[KIN_NY])) { status = VC_KIN_ROUNDING; break; }
     if (steps >= max_iter) { status = VC_KIN_MAX_ITER; break; }
     // a barely positive definite observed matrix throws the step out of the box: the Fisher step, which the priors bound, before giving up
     if (st.observed && !(__builtin_fabs(x + st.dx) <= KIN_BOUND && __builtin_fabs(y + st.dy) <= KIN_BOUND))
@@ -422,7 +352,7 @@ __global__ __launch_bounds__(KIN_NT) void vc_gene_kinetics_kernel(const void* __
       const double ux = tx - mx, uy = ty - my;
       const double pen2 = __builtin_fma(0.5 * px * ux, ux, 0.5 * py * uy * uy);
       const double A = acc[KIN_A] > Acur ? acc[KIN_A] : Acur;
-      if (acc[KIN_L] - pen2 >= fcur - 8.0 * KIN_EPS32 * A) {         // false for a NaN: such a step is halved
+      if (acc[KIN_L] - pen2 >= fcur - 8.0 * GENE_EPS32 * A) {         // false for a NaN: such a step is halved
         x = tx;
         y = ty;
         moved = true;
@@ -466,10 +396,7 @@ __global__ __launch_bounds__(KIN_NT) void vc_gene_kinetics_kernel(const void* __
   }
 }
 
-int kin_fail(int code, const char* msg) {
-  vc_set_global_error(msg);
-  return code;
-}
+constexpr char KIN_FN[] = "vc_gene_kinetics";
 
 }  // namespace
 
@@ -478,24 +405,19 @@ extern "C" int vc_gene_kinetics(const void* counts_dev, int count_kind, int64_t 
                                 int noise, const float* r_dev, const double* prior_dev, const double* start_dev, double tol, int max_iter,
                                 double* xy_dev, double* cov_dev, double* loglik_dev, double* dec_dev, int32_t* iterations_dev,
                                 int32_t* status_dev, int32_t* n_clamped_dev, double* score_w_dev, double* info_w_dev, void* hip_stream) {
-  if (noise == VC_NOISE_LOGNORMAL) return kin_fail(VC_ERR_UNSUPPORTED, "vc_gene_kinetics: Lognormal noise is not implemented (Poisson or NegativeBinomial)");
-  if (noise != VC_NOISE_NB && noise != VC_NOISE_POISSON) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: noise must be VC_NOISE_POISSON or VC_NOISE_NB");
-  if (count_kind != VC_COUNTS_F32 && count_kind != VC_COUNTS_U16) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: count_kind must be VC_COUNTS_F32 or VC_COUNTS_U16");
-  if (K == 7) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: K must be 3 or 5: H = 3 is not instantiated");
-  if (K != 3 && K != 5) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: K must be 3 or 5 (2 H + 1, H in {1, 2}; H = 0 has no velocity)");
-  if (NW < 0 || NW > 3) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: NW must be in 0..3 (rows of the angular speed's design)");
-  if (Ng < 1 || Nc < 1) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: Ng and Nc must be >= 1");
-  if (Ng > 0x7fffffffLL || Nc > 0x7fffffffLL) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: more than 2^31 - 1 genes or cells in one call");
-  if (gene_stride < Nc) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: gene_stride < Nc");
-  if (max_iter < 0) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: max_iter must be >= 0");
-  if (!(tol >= 0.0)) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: tol must be >= 0");
-  if (!counts_dev || !basis_dev || !logm_dev || !nu_dev || !prior_dev) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: null input pointer");
-  if (!xy_dev || !cov_dev || !loglik_dev || !dec_dev || !iterations_dev || !status_dev || !n_clamped_dev) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: null output pointer");
-  if (NW > 0 && (!w_dev || !nuw_dev)) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: NW > 0 needs w_dev and nuw_dev");
-  if (NW > 0 && (!score_w_dev || !info_w_dev)) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: NW > 0 needs score_w_dev and info_w_dev (the NW outputs)");
-  if (noise == VC_NOISE_NB && !r_dev) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: the negative binomial needs r_dev (1 / dispersion per gene)");
-  if (max_iter == 0 && !start_dev) return kin_fail(VC_ERR_ARG, "vc_gene_kinetics: max_iter == 0 (evaluate only) needs start_dev");
-  const dim3 grid((unsigned)Ng), block(KIN_NT);
+  const char* own = nullptr;                                         // what only this entry point says, reported in its place among the shared refusals
+  if (K == 7) own = "K must be 3 or 5: H = 3 is not instantiated";
+  else if (K != 3 && K != 5) own = "K must be 3 or 5 (2 H + 1, H in {1, 2}; H = 0 has no velocity)";
+  else if (NW < 0 || NW > 3) own = "NW must be in 0..3 (rows of the angular speed's design)";
+  const int refused = gene_refuse(KIN_FN, noise, count_kind, own, Ng, Nc, true, gene_stride, 0, max_iter, tol);
+  if (refused != VC_OK) return refused;
+  if (!counts_dev || !basis_dev || !logm_dev || !nu_dev || !prior_dev) return gene_fail(KIN_FN, VC_ERR_ARG, "null input pointer");
+  if (!xy_dev || !cov_dev || !loglik_dev || !dec_dev || !iterations_dev || !status_dev || !n_clamped_dev) return gene_fail(KIN_FN, VC_ERR_ARG, "null output pointer");
+  if (NW > 0 && (!w_dev || !nuw_dev)) return gene_fail(KIN_FN, VC_ERR_ARG, "NW > 0 needs w_dev and nuw_dev");
+  if (NW > 0 && (!score_w_dev || !info_w_dev)) return gene_fail(KIN_FN, VC_ERR_ARG, "NW > 0 needs score_w_dev and info_w_dev (the NW outputs)");
+  if (noise == VC_NOISE_NB && !r_dev) return gene_fail(KIN_FN, VC_ERR_ARG, "the negative binomial needs r_dev (1 / dispersion per gene)");
+  if (max_iter == 0 && !start_dev) return gene_fail(KIN_FN, VC_ERR_ARG, "max_iter == 0 (evaluate only) needs start_dev");
+  const dim3 grid((unsigned)Ng), block(GENE_NT);
   hipStream_t st = (hipStream_t)hip_stream;
 #define KIN_LAUNCH(H, NW_, NOISE, U16)                                                                                                 \
   hipLaunchKernelGGL((vc_gene_kinetics_kernel<H, NW_, NOISE, U16>), grid, block, 0, st, counts_dev, (long long)Nc,                     \
@@ -519,10 +441,5 @@ extern "C" int vc_gene_kinetics(const void* counts_dev, int count_kind, int64_t 
 #undef KIN_LAUNCH_H
 #undef KIN_LAUNCH_S
 #undef KIN_LAUNCH
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    try { vc_set_global_error((std::string("vc_gene_kinetics: launch failed: ") + hipGetErrorString(err)).c_str()); } catch (...) {}
-    return VC_ERR_HIP;
-  }
-  return VC_OK;
+  return gene_launched(KIN_FN);
 }

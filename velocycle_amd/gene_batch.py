@@ -24,9 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gene_harmonics import (GeneHarmonicFit, _check_run_options, _constants, _open_device, _ptr, _stage, check_arguments,
-                             default_chunk_genes)
-from .phase_mle import _is_sparse
+from .gene_harmonics import GeneHarmonicFit, _check_run_options, _chunks, _constants, _open_device, _ptr, _unpack_tri, check_arguments
 
 MAX_BATCHES = _lib.VC_GLM_MAX_BATCHES
 
@@ -131,8 +129,6 @@ def gene_harmonics_batched(counts, directions, n_scounts, batches, harmonics=1, 
     lib, dev, HipEngineError = _open_device(device)
     K = basis.shape[0]
     NH = K * (K + 1) // 2
-    if _is_sparse(counts):
-        counts = counts.tocsc()
     ptr = _ptr
     with torch.cuda.device(dev):
         perm_d = torch.from_numpy(perm).to(dev)
@@ -148,11 +144,8 @@ def gene_harmonics_batched(counts, directions, n_scounts, batches, harmonics=1, 
         full = dict(nu=f64(Ng, K), delta=f64(Ng, Nb), cov=f64(Ng, NH), dvar=f64(Ng, Nb), ll=f64(Ng), dec=f64(Ng), it=i32(), st=i32())
         null = dict(nu=f64(Ng, 1), delta=f64(Ng, Nb), cov=f64(Ng, 1), dvar=f64(Ng, Nb), ll=f64(Ng), dec=f64(Ng), it=i32(), st=i32())
         const = f64(Ng)
-        step = int(chunk_genes) if chunk_genes is not None else default_chunk_genes(Nc)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for g0 in range(0, Ng, step):
-            g1 = min(Ng, g0 + step)
-            blk, kblk, kind = _stage(counts, g0, g1, Nc, dev, storage)
+        for g0, g1, blk, kblk, kind in _chunks(counts, Nc, Ng, dev, storage, chunk_genes):
             same = kblk is blk
             blk = blk[:, perm_d].contiguous()                                        # cells of a batch contiguous, batches in order
             kblk = blk if same else kblk[:, perm_d].contiguous()
@@ -169,10 +162,7 @@ def gene_harmonics_batched(counts, directions, n_scounts, batches, harmonics=1, 
                     raise HipEngineError(f"vc_gene_glm_batch failed ({rc}): {lib.vc_last_error(None).decode()}")
             torch.cuda.current_stream(dev).synchronize()                             # the block and the slices outlive their launches
             del blk, kblk
-        tri = torch.tril_indices(K, K)
-        cov = torch.zeros((Ng, K, K), dtype=torch.float64, device=dev)
-        cov[:, tri[0], tri[1]] = full["cov"]                                      # packed row by row: the order of tril_indices
-        cov[:, tri[1], tri[0]] = full["cov"]
+        cov = _unpack_tri(full["cov"], K)
         stds = torch.sqrt(torch.diagonal(cov, dim1=1, dim2=2))
         return GeneBatchHarmonicFit(means=full["nu"].T.cpu().numpy().copy(), stds=stds.T.cpu().numpy().copy(), cov=cov.cpu().numpy(),
                                     loglik=(full["ll"] + const).cpu().numpy(), loglik_null=(null["ll"] + const).cpu().numpy(),

@@ -169,16 +169,9 @@ def gene_totals(counts):
     return tot
 
 
-def check_arguments(counts, directions, n_scounts, harmonics, a, noisemodel, dispersion, prior_means=None, prior_stds=None,
-                    tol=1e-10, max_iter=25):
-    """Every refusal that needs no device.  Returns (basis float64 [K, Nc], logm float64 [Nc], r float64 [Ng] or None,
-    prior means float64 [Ng, K] or None, prior precisions float64 [Ng, K] or None)."""
-    if noisemodel not in NOISEMODELS:
-        raise NotImplementedError("Not implemented yet, sorry")
-    if int(harmonics) != harmonics or not 0 <= harmonics <= MAX_HARMONICS:
-        raise ValueError(f"harmonics must be an integer in 0..{MAX_HARMONICS}")
-    harmonics = int(harmonics)
-    K = 2 * harmonics + 1
+def _check_cells(counts, directions, n_scounts, tol, max_iter):
+    """The refusals every per-gene worker makes of the counts' shape, the directions, n_scounts, tol and max_iter.  Returns
+    (Nc, Ng, directions float64 [2, Nc], n_scounts float64 [Nc])."""
     if len(counts.shape) != 2 or counts.shape[0] < 1 or counts.shape[1] < 1:
         raise ValueError("counts must be [cells, genes] with at least one of each")
     Nc, Ng = int(counts.shape[0]), int(counts.shape[1])
@@ -197,14 +190,33 @@ def check_arguments(counts, directions, n_scounts, harmonics, a, noisemodel, dis
         raise ValueError("tol must be >= 0")
     if int(max_iter) != max_iter or max_iter < 1:
         raise ValueError("max_iter must be an integer >= 1")
-    r = None
-    if noisemodel == "NegativeBinomial":
-        d = torch.as_tensor(np.asarray(dispersion, dtype=np.float64)).reshape(-1)
-        if d.numel() not in (1, Ng):
-            raise ValueError(f"dispersion must be a scalar or one value per gene ({Ng}), got {d.numel()}")
-        if not bool((torch.isfinite(d) & (d > 0)).all()):
-            raise ValueError("dispersion must be > 0")
-        r = (1.0 / d).expand(Ng).contiguous()
+    return Nc, Ng, xy, n
+
+
+def _dispersion_to_r(noisemodel, dispersion, Ng):
+    """r = 1 / dispersion, float64 [Ng], of the negative binomial (dispersion: a scalar or one value per gene, > 0); None for Poisson."""
+    if noisemodel != "NegativeBinomial":
+        return None
+    d = torch.as_tensor(np.asarray(dispersion, dtype=np.float64)).reshape(-1)
+    if d.numel() not in (1, Ng):
+        raise ValueError(f"dispersion must be a scalar or one value per gene ({Ng}), got {d.numel()}")
+    if not bool((torch.isfinite(d) & (d > 0)).all()):
+        raise ValueError("dispersion must be > 0")
+    return (1.0 / d).expand(Ng).contiguous()
+
+
+def check_arguments(counts, directions, n_scounts, harmonics, a, noisemodel, dispersion, prior_means=None, prior_stds=None,
+                    tol=1e-10, max_iter=25):
+    """Every refusal that needs no device.  Returns (basis float64 [K, Nc], logm float64 [Nc], r float64 [Ng] or None,
+    prior means float64 [Ng, K] or None, prior precisions float64 [Ng, K] or None)."""
+    if noisemodel not in NOISEMODELS:
+        raise NotImplementedError("Not implemented yet, sorry")
+    if int(harmonics) != harmonics or not 0 <= harmonics <= MAX_HARMONICS:
+        raise ValueError(f"harmonics must be an integer in 0..{MAX_HARMONICS}")
+    harmonics = int(harmonics)
+    K = 2 * harmonics + 1
+    Nc, Ng, xy, n = _check_cells(counts, directions, n_scounts, tol, max_iter)
+    r = _dispersion_to_r(noisemodel, dispersion, Ng)
     if (prior_means is None) != (prior_stds is None):
         raise ValueError("a prior needs both prior_means and prior_stds")
     pm = pp = None
@@ -281,6 +293,27 @@ def _stage(counts, g0, g1, Nc, dev, storage):
     if storage != "f32" and hi <= 65535:
         return blk, u16_bits(blk), _lib.VC_COUNTS_U16
     return blk, blk, _lib.VC_COUNTS_F32
+
+
+def _chunks(counts, Nc, Ng, dev, storage, chunk_genes):
+    """The genes in chunks of `chunk_genes` (None: `default_chunk_genes`), each staged on the device as it is asked for: yields
+    (g0, g1, the float32 block, the block the kernels read, its count kind).  Nothing here keeps a block: whoever iterates drops his
+    (`del`) once the launches that read it are through, before he asks for the next."""
+    if _is_sparse(counts):
+        counts = counts.tocsc()
+    step = int(chunk_genes) if chunk_genes is not None else default_chunk_genes(Nc)
+    for g0 in range(0, Ng, step):
+        g1 = min(Ng, g0 + step)
+        yield (g0, g1, *_stage(counts, g0, g1, Nc, dev, storage))
+
+
+def _unpack_tri(packed, K):
+    """[n, K (K + 1) / 2] lower triangles packed row by row (the order of tril_indices) -> the symmetric matrices [n, K, K]."""
+    tri = torch.tril_indices(K, K)
+    full = torch.zeros((packed.shape[0], K, K), dtype=packed.dtype, device=packed.device)
+    full[:, tri[0], tri[1]] = packed
+    full[:, tri[1], tri[0]] = packed
+    return full
 
 
 def _check_run_options(storage, chunk_genes):
@@ -360,8 +393,6 @@ def gene_harmonics(counts, directions, n_scounts, harmonics=1, a=1, noisemodel="
     lib, dev, HipEngineError = _open_device(device)
     K = basis.shape[0]
     NH = K * (K + 1) // 2
-    if _is_sparse(counts):
-        counts = counts.tocsc()
     ptr = _ptr
     with torch.cuda.device(dev):
         B_d = basis.to(torch.float32).to(dev).contiguous()
@@ -387,12 +418,9 @@ def gene_harmonics(counts, directions, n_scounts, harmonics=1, a=1, noisemodel="
             extra = {n: torch.empty(Ng, dtype=torch.float64, device=dev) for n in ("r", "rho", "info", "llp", "constp")}
             dstatus = torch.empty(Ng, dtype=torch.int32, device=dev)
             rounds = torch.empty(Ng, dtype=torch.int32, device=dev)
-        step = int(chunk_genes) if chunk_genes is not None else default_chunk_genes(Nc)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for g0 in range(0, Ng, step):
-            g1 = min(Ng, g0 + step)
+        for g0, g1, blk, kblk, kind in _chunks(counts, Nc, Ng, dev, storage, chunk_genes):
             n = g1 - g0
-            blk, kblk, kind = _stage(counts, g0, g1, Nc, dev, storage)
 
             def glm(k_, noise, r_c, pm_c, pp_c, outs):
                 rc = lib.vc_gene_glm(ptr(kblk), kind, n, Nc, Nc, ptr(B_d), k_, ptr(logm_d), _lib.NOISE[noise], ptr(r_c), ptr(pm_c),
@@ -444,10 +472,7 @@ def gene_harmonics(counts, directions, n_scounts, harmonics=1, a=1, noisemodel="
                 extra["constp"][g0:g1] = _constants(blk, None)
             torch.cuda.current_stream(dev).synchronize()                             # the block and the slices outlive their launches
             del blk, kblk
-        tri = torch.tril_indices(K, K)
-        full = torch.zeros((Ng, K, K), dtype=torch.float64, device=dev)
-        full[:, tri[0], tri[1]] = cov                                              # packed row by row: the order of tril_indices
-        full[:, tri[1], tri[0]] = cov
+        full = _unpack_tri(cov, K)
         stds = torch.sqrt(torch.diagonal(full, dim1=1, dim2=2))
         fit = GeneHarmonicFit(means=nu.T.cpu().numpy().copy(), stds=stds.T.cpu().numpy().copy(), cov=full.cpu().numpy(),
                               loglik=(out["ll"] + const).cpu().numpy(), loglik_null=(out["ll0"] + const0).cpu().numpy(),
@@ -492,8 +517,6 @@ def gene_dispersion(counts, directions, n_scounts, means, a=1, *, start=None, pr
     pa, pb = _dispersion_prior(prior, Ng)
     lib, dev, HipEngineError = _open_device(device)
     K = basis.shape[0]
-    if _is_sparse(counts):
-        counts = counts.tocsc()
     ptr = _ptr
     with torch.cuda.device(dev):
         B_d = basis.to(torch.float32).to(dev).contiguous()
@@ -506,11 +529,8 @@ def gene_dispersion(counts, directions, n_scounts, means, a=1, *, start=None, pr
         r_out = torch.empty(Ng, dtype=torch.float32, device=dev)
         iters = torch.empty(Ng, dtype=torch.int32, device=dev)
         status = torch.empty(Ng, dtype=torch.int32, device=dev)
-        step = int(chunk_genes) if chunk_genes is not None else default_chunk_genes(Nc)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for g0 in range(0, Ng, step):
-            g1 = min(Ng, g0 + step)
-            blk, kblk, kind = _stage(counts, g0, g1, Nc, dev, storage)
+        for g0, g1, blk, kblk, kind in _chunks(counts, Nc, Ng, dev, storage, chunk_genes):
             out["const"][g0:g1] = _constants(blk, None)
             sl = lambda t: t[g0:g1] if t is not None else None                       # noqa: E731
             rc = lib.vc_gene_dispersion(ptr(kblk), kind, g1 - g0, Nc, Nc, ptr(B_d), K, ptr(logm_d), ptr(nu_d[g0:g1]), ptr(sl(r_d)),

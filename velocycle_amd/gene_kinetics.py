@@ -25,9 +25,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gene_harmonics import (_check_run_options, _constants, _open_device, _ptr, _row_sums, _stage, default_chunk_genes,
-                             fourier_basis_from_directions)
-from .phase_mle import NOISEMODELS, _is_sparse
+from .gene_harmonics import (_check_cells, _check_run_options, _chunks, _constants, _dispersion_to_r, _open_device, _ptr, _row_sums,
+                             _unpack_tri, fourier_basis_from_directions)
+from .phase_mle import NOISEMODELS
 
 HARMONICS = (1, 2)                   # csrc/vc_gene_kinetics.hip
 MAX_NW = 3
@@ -103,34 +103,10 @@ def check_arguments(counts, directions, n_scounts, means, a=1, noisemodel="Poiss
     if nu.ndim != 2 or nu.shape[0] not in (3, 5):
         raise ValueError(f"means must be [2 harmonics + 1, genes] with 1 or 2 harmonics (3 are not instantiated, 0 have no velocity), "
                          f"got {nu.shape}")
-    if len(counts.shape) != 2 or counts.shape[0] < 1 or counts.shape[1] < 1:
-        raise ValueError("counts must be [cells, genes] with at least one of each")
-    Nc, Ng = int(counts.shape[0]), int(counts.shape[1])
+    Nc, Ng, xy, n = _check_cells(counts, directions, n_scounts, tol, max_iter)
     if nu.shape[1] != Ng:
         raise ValueError(f"means has {nu.shape[1]} genes, counts {Ng}")
-    xy = np.asarray(directions, dtype=np.float64)
-    if xy.shape != (2, Nc):
-        raise ValueError(f"directions must be [2, cells] = (2, {Nc}) like Phases.phi_xy, got {xy.shape}")
-    norm2 = xy[0] ** 2 + xy[1] ** 2
-    if not (np.isfinite(norm2).all() and (norm2 > 0).all()):
-        raise ValueError("every cell needs a finite phase direction of non-zero length")
-    n = np.asarray(n_scounts, dtype=np.float64).reshape(-1)
-    if n.size != Nc:
-        raise ValueError(f"n_scounts has {n.size} entries for {Nc} cells")
-    if not (np.isfinite(n).all() and (n > 0).all()):
-        raise ValueError("every cell needs a finite n_scounts > 0")
-    if not (tol >= 0):
-        raise ValueError("tol must be >= 0")
-    if int(max_iter) != max_iter or max_iter < 1:
-        raise ValueError("max_iter must be an integer >= 1")
-    r = None
-    if noisemodel == "NegativeBinomial":
-        d = torch.as_tensor(np.asarray(dispersion, dtype=np.float64)).reshape(-1)
-        if d.numel() not in (1, Ng):
-            raise ValueError(f"dispersion must be a scalar or one value per gene ({Ng}), got {d.numel()}")
-        if not bool((torch.isfinite(d) & (d > 0)).all()):
-            raise ValueError("dispersion must be > 0")
-        r = (1.0 / d).expand(Ng).contiguous()
+    r = _dispersion_to_r(noisemodel, dispersion, Ng)
     if prior is None or len(prior) != 4:
         raise ValueError("the prior is (mu_gamma, sd_gamma, mu_beta, sd_beta) of log gamma and log beta")
     cols = []
@@ -174,8 +150,6 @@ class _Problem:
         self.Nc, self.Ng, self.K = int(counts.shape[0]), int(counts.shape[1]), int(basis.shape[0])
         self.noise = _lib.NOISE[noisemodel]
         dev = self.dev
-        if _is_sparse(counts):
-            counts = counts.tocsc()
         with torch.cuda.device(dev):
             self.B = basis.to(torch.float32).to(dev).contiguous()
             self.logm = logm.to(torch.float32).to(dev).contiguous()
@@ -184,11 +158,8 @@ class _Problem:
             r64 = self.r.double() if self.r is not None else None                # the model is the one of the float32 r the kernel reads
             self.prior = torch.as_tensor(prior).to(dev).contiguous()
             self.const = torch.empty(self.Ng, dtype=torch.float64, device=dev)
-            step = int(chunk_genes) if chunk_genes is not None else default_chunk_genes(self.Nc)
             self.chunks = []
-            for g0 in range(0, self.Ng, step):
-                g1 = min(self.Ng, g0 + step)
-                blk, kblk, kind = _stage(counts, g0, g1, self.Nc, dev, storage)
+            for g0, g1, blk, kblk, kind in _chunks(counts, self.Nc, self.Ng, dev, storage, chunk_genes):
                 self.const[g0:g1] = _constants(blk, r64[g0:g1] if r64 is not None else None)
                 self.chunks.append((g0, g1, kblk, kind))
                 del blk
@@ -226,10 +197,7 @@ class _Problem:
 
     def fit(self, out):
         NW = out["score"].shape[1]
-        tri = torch.tril_indices(NW, NW)
-        info = torch.zeros((self.Ng, NW, NW), dtype=torch.float64, device=self.dev)
-        info[:, tri[0], tri[1]] = out["info"]
-        info[:, tri[1], tri[0]] = out["info"]
+        info = _unpack_tri(out["info"], NW)
         c = out["cov"]
         cov = torch.stack([torch.stack([c[:, 0], c[:, 1]], 1), torch.stack([c[:, 1], c[:, 2]], 1)], 1)
         return GeneKineticsFit(log_gamma=out["xy"][:, 0].cpu().numpy().copy(), log_beta=out["xy"][:, 1].cpu().numpy().copy(),
