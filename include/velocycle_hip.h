@@ -40,6 +40,8 @@
  *                               negative-binomial log-link regression on the Fourier design per gene; stand-alone, no engine
  *   vc_gene_glm_batch           no counterpart: vc_gene_glm with the phase model's per-batch offsets (phase_inference_model.py: ElogS =
  *                               nu . zeta + Db . dnu + count_factor), nu and dnu estimated jointly per gene; stand-alone, no engine
+ *   vc_gene_glm_weighted        no counterpart: vc_gene_glm with case weights per cell, R rows of weights per call (the cell bootstrap
+ *                               of the harmonic fit, held-out fits, weighted regression); stand-alone, no engine
  *   vc_gene_dispersion          no counterpart (the reference learns shape_inv only inside the SVI, velocity_inference_model.py:383):
  *                               the maximum-likelihood (or Gamma-prior mode) negative-binomial dispersion per gene with the means of
  *                               vc_gene_glm known; stand-alone, no engine
@@ -594,6 +596,40 @@ int vc_gene_glm_batch(const void* counts_dev, int count_kind, int64_t Ng, int64_
                       const double* prior_prec_dev, double tol, int max_iter, double* nu_dev, double* delta_dev, double* cov_nu_dev,
                       double* delta_var_dev, double* loglik_dev, double* dec_dev, int32_t* iterations_dev, int32_t* status_dev,
                       void* hip_stream);
+
+/* --- per-gene harmonic regression with case weights (stand-alone: no engine handle) -------------------------------------------
+ * vc_gene_glm with every cell's contribution multiplied by a weight w_bc >= 0: one call solves R rows of weights for every gene (a
+ * cell bootstrap: Poisson(1) integers per row; a held-out fit: 0 / 1; the ordinary weighted regression: the caller's weights).  One
+ * workgroup per (gene, row), grid (R, genes) with the row as the fast index, one launch per 65535 genes, no workspace, no allocation, no synchronisation; asynchronous on hip_stream.
+ * counts_dev, count_kind, Ng, Nc, gene_stride, basis_dev, K, logm_dev, noise, r_dev, prior_mean_dev, prior_prec_dev, tol, max_iter:
+ * as for vc_gene_glm.  Every pointer is DEVICE memory.
+ *   weights_dev     float: w_bc at index b * weight_stride + c (weight_stride >= Nc; what lies between Nc and the stride is not read).
+ *                   Weights are taken to be finite and >= 0 (device memory is not read before the launch); a row with a NaN weight ends
+ *                   VC_GLM_UNBOUNDED like a row without counts
+ *   R               rows of weights, 1..65535 per call
+ *   start_dev       NULL, or double[Ng][K]: where every entry of gene g is finite and its harmonics lie in [-50, 50], the first point of
+ *                   every row of gene g (the bootstrap warm-starts from the full-data fit); otherwise the row's default start
+ * With wt = (double)w_bc and res, wo, term, mag the per-element numbers of vc_gene_glm:
+ *   gradient sum_c (wt res) B_i      Hessian sum_c (wt wo) B_i B_j      objective sum_c wt term      A = sum_c wt mag
+ *   N_i = sum_c ((wt wo)^2 + (wt res)^2) B_i^2                            default start nu_0 = ln(sum_c wt k / sum_c wt e^logm)
+ * The negative binomial's r ln r is inside term and weighted with it; the prior is not weighted.  Each product with wt is formed first and
+ * is exact at wt == 1; the float64 operations that follow, the fold, the K x K algebra, the step rules (halving, the [-50, 50] bound,
+ * VC_GLM_ROUNDING on the weighted N_i, max_iter) and the status codes are vc_gene_glm's.  A row whose sum_c wt k is not a positive finite
+ * number (or whose default nu_0 is not finite) ends VC_GLM_UNBOUNDED with the outputs vc_gene_glm gives a gene without counts: nu_0 as
+ * formed (-inf or NaN), harmonics 0, cov, loglik and dec NaN, 0 iterations -- whatever start_dev holds.
+ * Outputs, of row b and gene g at index b * Ng + g:
+ *   nu_dev double[R][Ng][K];  cov_dev NULL (not stored) or double[R][Ng][K (K + 1) / 2], packed as vc_gene_glm's;
+ *   loglik_dev, dec_dev double[R][Ng];  iterations_dev, status_dev int32[R][Ng]
+ * Bits: identical under repetition; identical between uint16 and float32 storage; identical under any cutting of the genes or of the
+ * rows into calls (row b of an R-row call equals the call on that row alone); with a table of ones, R = 1 and start_dev NULL every
+ * output equals vc_gene_glm's on the same inputs bit for bit.  A (gene, row) pair's status touches no other pair's outputs; every path
+ * is bounded.  VC_ERR_ARG / VC_ERR_UNSUPPORTED as vc_gene_glm's in its order (cov_dev may be NULL here), then weights_dev NULL, R outside
+ * 1..65535, weight_stride < Nc: all decided before anything is launched.  Errors: vc_last_error(NULL). */
+int vc_gene_glm_weighted(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* basis_dev,
+                         int K, const float* logm_dev, int noise, const float* r_dev, const double* prior_mean_dev,
+                         const double* prior_prec_dev, const float* weights_dev, int64_t R, int64_t weight_stride,
+                         const double* start_dev, double tol, int max_iter, double* nu_dev, double* cov_dev, double* loglik_dev,
+                         double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, void* hip_stream);
 
 /* --- per-gene negative-binomial dispersion given the means (stand-alone: no engine handle) -----------------------------------
  * The third factor of the model of vc_gene_glm: with eta_c = nu_g . basis[:, c] + logm[c], mu = exp(eta) known, maximise over

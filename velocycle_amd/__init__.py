@@ -5,3 +5,14 @@ The per-step ELBO + reparameterised gradient runs in hand-written HIP kernels fo
 Python host side mirroring the reference's `fit()` entry points.
 """
 __version__ = "0.1.0"
+
+# names served from their modules on first use (importing the package stays free of torch)
+_LAZY = {"gene_harmonics_bootstrap": "gene_bootstrap", "GeneHarmonicBootstrap": "gene_bootstrap"}
+__all__ = sorted(_LAZY)
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        from importlib import import_module
+        return getattr(import_module(f".{_LAZY[name]}", __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

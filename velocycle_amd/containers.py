@@ -144,10 +144,19 @@ class Cycle(_HarmonicTable):
         `Phases.from_cycle_mle(cycle, data, noisemodel="NegativeBinomial", dispersion=cycle.disp_pyro)` consumes; the layer may
         be dense or sparse.  Keyword-only: `layer`, `prior`, `return_fit=True` returns (Cycle, GeneHarmonicFit) -- the fit holds the
         log-likelihoods, the likelihood-ratio statistic for periodicity and its p-value, and how every gene's iteration ended; anything
-        else goes to the worker (tol, max_iter, device, chunk_genes, storage)."""
+        else goes to the worker (tol, max_iter, device, chunk_genes, storage).  `bootstrap=n > 0` (by name, default 0): the Cycle's
+        stds are those of n cell bootstrap replicates (`velocycle_amd.gene_bootstrap.gene_harmonics_bootstrap`, seeded by
+        `bootstrap_seed`, default 0) instead of the Hessian's, which understate the spread whenever the noise model does; the means
+        are unchanged, and with `return_fit=True` the fit carries the `GeneHarmonicBootstrap` as `fit.bootstrap`.  Not with
+        `dispersion="mle"`."""
         from .gene_harmonics import NOISEMODELS, gene_harmonics
         if noisemodel not in NOISEMODELS:
             raise NotImplementedError("Not implemented yet, sorry")
+        bootstrap, bootstrap_seed = worker_kw.pop("bootstrap", 0), worker_kw.pop("bootstrap_seed", 0)      # by name only
+        if int(bootstrap) != bootstrap or bootstrap < 0:
+            raise ValueError("bootstrap must be an integer >= 0 (the number of replicates)")
+        if bootstrap and isinstance(dispersion, str):
+            raise ValueError("bootstrap with dispersion='mle' is not supported: vc_gene_dispersion knows no weights")
         if layer not in data.layers:
             raise ValueError(f"{layer=} is not a layer of the data")
         counts = data.layers[layer]
@@ -171,8 +180,17 @@ class Cycle(_HarmonicTable):
         fit = gene_harmonics(counts, np.asarray(phases.phi_xy.values, dtype=np.float64), np.asarray(data.obs.n_scounts.values),
                              harmonics=harmonics, a=a, noisemodel=noisemodel, dispersion=dispersion, prior_means=prior_means,
                              prior_stds=prior_stds, **worker_kw)
-        out = cls.from_array(fit.means, fit.stds, gene_names=data.var.index)
-        if fit.dispersion is not None:                                   # dispersion="mle": the field the reference keeps shape_inv in
+        stds = fit.stds
+        if bootstrap:
+            from .gene_bootstrap import gene_harmonics_bootstrap
+            run_kw = {k: worker_kw[k] for k in ("tol", "max_iter", "device", "chunk_genes", "storage") if k in worker_kw}
+            fit.bootstrap = gene_harmonics_bootstrap(counts, np.asarray(phases.phi_xy.values, dtype=np.float64),
+                                                     np.asarray(data.obs.n_scounts.values), harmonics=harmonics, a=a,
+                                                     noisemodel=noisemodel, dispersion=dispersion, n_boot=int(bootstrap),
+                                                     seed=bootstrap_seed, fit=fit, prior_means=prior_means, prior_stds=prior_stds, **run_kw)
+            stds = fit.bootstrap.stds
+        out = cls.from_array(fit.means, stds, gene_names=data.var.index)
+        if fit.dispersion is not None:                                  # dispersion="mle": the field the reference keeps shape_inv in
             out.set_disp_pyro(fit.dispersion)
         return (out, fit) if return_fit else out
 

@@ -29,6 +29,8 @@
 //            accepted unless L' < L - 8 eps32 max(A, A') (a drop beyond the objective's own rounding), else t /= 2; a gene has
 //            GLM_MAX_HALVINGS halvings in all (then MAX_ITER): no path spins.
 // Outputs are those of the last accepted point: nu, packed H^-1, L without the prior term, dec, steps taken, status.
+// vc_gene_glm_weighted.hip repeats glm_factor, the start, this iteration and the covariance block statement for statement (with case
+// weights in its sweep): a change to the step or stopping rules has to be made in both files.
 #include "vc_gene_glm_math.h"                     // glm_sweep, glm_prior and the packed algebra, shared with vc_gene_glm_batch.hip; through it vc_gene_math.h
 
 #pragma clang fp contract(off)

@@ -65,6 +65,7 @@ class GeneHarmonicFit:
     rounds: InitVar[np.ndarray] = None
     loglik_poisson: InitVar[np.ndarray] = None
     overdispersion_p: InitVar[np.ndarray] = None
+    bootstrap = None                 # `Cycle.from_phases_mle(bootstrap=n)` hangs its GeneHarmonicBootstrap here: an attribute, not a field
 
     def __post_init__(self, dispersion, log_r_std, dispersion_status, rounds, loglik_poisson, overdispersion_p):
         self.dispersion, self.log_r_std, self.dispersion_status = dispersion, log_r_std, dispersion_status
@@ -205,6 +206,27 @@ def _dispersion_to_r(noisemodel, dispersion, Ng):
     return (1.0 / d).expand(Ng).contiguous()
 
 
+MAX_WEIGHT_ROWS = 65535              # csrc/vc_gene_glm_weighted.hip: rows of weights per call
+
+
+def check_weights(weights, Nc, rows=None):
+    """Case weights as the contiguous float32 host table [R, Nc] `vc_gene_glm_weighted` reads: finite and >= 0, R in 1..65535
+    (rows=1: a vector [Nc] for `gene_harmonics`)."""
+    w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
+    if rows == 1:
+        if w.shape != (Nc,):
+            raise ValueError(f"cell_weights must be one weight per cell ({Nc},), got {w.shape}")
+        w = w[None, :]
+    if w.ndim != 2 or w.shape[1] != Nc or w.shape[0] < 1:
+        raise ValueError(f"weights must be [rows, cells] = (R, {Nc}), got {w.shape}")
+    if w.shape[0] > MAX_WEIGHT_ROWS:
+        raise ValueError(f"at most {MAX_WEIGHT_ROWS} rows of weights, got {w.shape[0]}")
+    w32 = np.ascontiguousarray(w, dtype=np.float32)
+    if not (np.isfinite(w32).all() and (w >= 0).all()):
+        raise ValueError("weights must be finite and >= 0")
+    return w32
+
+
 def check_arguments(counts, directions, n_scounts, harmonics, a, noisemodel, dispersion, prior_means=None, prior_stds=None,
                     tol=1e-10, max_iter=25):
     """Every refusal that needs no device.  Returns (basis float64 [K, Nc], logm float64 [Nc], r float64 [Ng] or None,
@@ -267,9 +289,10 @@ def _row_sums(x):
     return x[:, 0]
 
 
-def _constants(blk, r64):
+def _constants(blk, r64, w64=None):
     """The part of every gene's log-likelihood that does not depend on nu and that the kernel leaves out, float64 [n]:
-    -lgamma(k + 1), and for the negative binomial lgamma(k + r) - lgamma(r) (its r log r is inside the kernel's objective)."""
+    -lgamma(k + 1), and for the negative binomial lgamma(k + r) - lgamma(r) (its r log r is inside the kernel's objective).
+    w64: float64 [Nc] case weights every cell's term is multiplied by (ones change no bit)."""
     out = torch.empty(blk.shape[0], dtype=torch.float64, device=blk.device)
     rows = max(1, (1 << 24) // blk.shape[1])
     for i in range(0, blk.shape[0], rows):
@@ -278,6 +301,8 @@ def _constants(blk, r64):
         if r64 is not None:
             rr = r64[i:i + rows, None]
             t += torch.lgamma(k + rr) - torch.lgamma(rr)
+        if w64 is not None:
+            t = t * w64[None, :]
         out[i:i + rows] = _row_sums(t)
     return out
 
@@ -370,7 +395,17 @@ def gene_harmonics(counts, directions, n_scounts, harmonics=1, a=1, noisemodel="
     every gene of the chunk is settled (`_alternate`) or `max_rounds` (10) rounds are spent, then `vc_gene_glm` once more at the final r.
     `dispersion_prior=(alpha, beta)` puts shape_inv ~ Gamma(alpha, beta) on the dispersion; `rho_tol` (1e-6) is the settling tolerance of
     ln r.  The null model has its own alternation, so `lr_stat` compares two maximised likelihoods.  These four are accepted by name only
-    and do nothing when `dispersion` is a number or an array."""
+    and do nothing when `dispersion` is a number or an array.
+
+    cell_weights (accepted by name only, default None): [Nc] finite case weights >= 0 (float32 on the device): every cell's term of the log-likelihood, of its
+    gradient and of its Hessian is multiplied by its weight, in the fit and in the null model alike, on the kernel
+    `vc_gene_glm_weighted` (one row of weights); `loglik` and `loglik_null` carry the weighted constants, `lr_stat` and `p_value` follow
+    from them.  A vector of ones returns the unweighted result bit for bit.  A gene without a count in any cell of positive weight ends
+    UNBOUNDED.  `dispersion="mle"` with weights is refused: `vc_gene_dispersion` knows no weights (nor do the batch and kinetics
+    workers).  `gene_bootstrap.gene_harmonics_bootstrap` solves many rows of weights per call."""
+    cell_weights = mle_options.pop("cell_weights", None)                             # by name only, like the options of "mle"
+    if cell_weights is not None and isinstance(dispersion, str):
+        raise ValueError("cell_weights with dispersion='mle' is not supported: vc_gene_dispersion knows no weights")
     unknown = set(mle_options) - set(MLE_OPTIONS)
     if unknown:
         raise TypeError(f"gene_harmonics() got unexpected keyword arguments {sorted(unknown)}")
@@ -389,12 +424,15 @@ def gene_harmonics(counts, directions, n_scounts, harmonics=1, a=1, noisemodel="
                                              opt["dispersion_start"] if mle else dispersion, prior_means, prior_stds, tol, max_iter)
     _check_run_options(storage, chunk_genes)
     Nc, Ng = int(counts.shape[0]), int(counts.shape[1])
+    w_host = check_weights(cell_weights, Nc, rows=1) if cell_weights is not None else None
     pa, pb = _dispersion_prior(opt["dispersion_prior"], Ng) if mle else (None, None)
     lib, dev, HipEngineError = _open_device(device)
     K = basis.shape[0]
     NH = K * (K + 1) // 2
     ptr = _ptr
     with torch.cuda.device(dev):
+        w_d = torch.from_numpy(w_host).to(dev).contiguous() if w_host is not None else None
+        w64 = w_d[0].double() if w_d is not None else None
         B_d = basis.to(torch.float32).to(dev).contiguous()
         logm_d = logm.to(torch.float32).to(dev).contiguous()
         r_d = r.to(torch.float32).to(dev).contiguous() if r is not None else None
@@ -423,6 +461,13 @@ def gene_harmonics(counts, directions, n_scounts, harmonics=1, a=1, noisemodel="
             n = g1 - g0
 
             def glm(k_, noise, r_c, pm_c, pp_c, outs):
+                if w_d is not None:                                              # one row of case weights, each gene from its default start
+                    rc = lib.vc_gene_glm_weighted(ptr(kblk), kind, n, Nc, Nc, ptr(B_d), k_, ptr(logm_d), _lib.NOISE[noise], ptr(r_c),
+                                                  ptr(pm_c), ptr(pp_c), ptr(w_d), 1, Nc, None, float(tol), int(max_iter),
+                                                  *[ptr(o) for o in outs], stream)
+                    if rc != _lib.VC_OK:
+                        raise HipEngineError(f"vc_gene_glm_weighted failed ({rc}): {lib.vc_last_error(None).decode()}")
+                    return
                 rc = lib.vc_gene_glm(ptr(kblk), kind, n, Nc, Nc, ptr(B_d), k_, ptr(logm_d), _lib.NOISE[noise], ptr(r_c), ptr(pm_c),
                                      ptr(pp_c), float(tol), int(max_iter), *[ptr(o) for o in outs], stream)
                 if rc != _lib.VC_OK:
@@ -435,7 +480,7 @@ def gene_harmonics(counts, directions, n_scounts, harmonics=1, a=1, noisemodel="
                        (nu[g0:g1], cov[g0:g1], out["ll"][g0:g1], out["dec"][g0:g1], iters[g0:g1], status[g0:g1])),
                       (1, pm0, pp0, (nu0[g0:g1], cov0[g0:g1], out["ll0"][g0:g1], dec0[g0:g1], it0[g0:g1], st0[g0:g1])))
             if not mle:
-                const[g0:g1] = _constants(blk, r64[g0:g1] if r64 is not None else None)
+                const[g0:g1] = _constants(blk, r64[g0:g1] if r64 is not None else None, w64)
                 r_c = r_d[g0:g1] if r_d is not None else None
                 for (k_, pm_c, pp_c, outs) in models:
                     glm(k_, noisemodel, r_c, pm_c, pp_c, outs)
