@@ -42,6 +42,8 @@
  *                               nu . zeta + Db . dnu + count_factor), nu and dnu estimated jointly per gene; stand-alone, no engine
  *   vc_gene_glm_weighted        no counterpart: vc_gene_glm with case weights per cell, R rows of weights per call (the cell bootstrap
  *                               of the harmonic fit, held-out fits, weighted regression); stand-alone, no engine
+ *   vc_gene_glm_batch_weighted  no counterpart: vc_gene_glm_batch with case weights per cell, R rows of weights per call (the cell
+ *                               bootstrap of the batch-aware fit: nu and dnu resampled jointly); stand-alone, no engine
  *   vc_gene_dispersion          no counterpart (the reference learns shape_inv only inside the SVI, velocity_inference_model.py:383):
  *                               the maximum-likelihood (or Gamma-prior mode) negative-binomial dispersion per gene with the means of
  *                               vc_gene_glm known; stand-alone, no engine
@@ -630,6 +632,45 @@ int vc_gene_glm_weighted(const void* counts_dev, int count_kind, int64_t Ng, int
                          const double* prior_prec_dev, const float* weights_dev, int64_t R, int64_t weight_stride,
                          const double* start_dev, double tol, int max_iter, double* nu_dev, double* cov_dev, double* loglik_dev,
                          double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, void* hip_stream);
+
+/* --- per-gene harmonic regression with per-batch offsets and case weights (stand-alone: no engine handle) ----------------------
+ * vc_gene_glm_batch with every cell's contribution multiplied by a weight w_bc >= 0, R rows of weights per call: the step
+ * vc_gene_glm_weighted takes from vc_gene_glm (the cell bootstrap of the batch-aware fit resamples nu and the offsets jointly).  One
+ * workgroup per (gene, row), grid (R, genes) with the row as the fast index, one launch per 65535 genes, the segment table in the
+ * kernel's arguments, no workspace, no allocation, no synchronisation; asynchronous on hip_stream.  counts_dev, count_kind, Ng, Nc,
+ * gene_stride, basis_dev, K, logm_dev, noise, r_dev, Nb, seg_host, delta_prior_mean_dev, delta_prior_prec_dev, prior_mean_dev,
+ * prior_prec_dev, tol, max_iter: as for vc_gene_glm_batch.  Every pointer but seg_host is DEVICE memory.
+ *   weights_dev     float: w_bc at index b * weight_stride + c (weight_stride >= Nc; what lies between Nc and the stride is not read),
+ *                   in the cell order of counts, basis and logm: the sorted one, with the segments of seg_host.  Weights are taken to
+ *                   be finite and >= 0 (device memory is not read before the launch)
+ *   R               rows of weights, 1..65535 per call
+ *   start_nu_dev, start_delta_dev   both NULL, or double[Ng][K] and double[Ng][Nb]: where every entry of gene g is finite, its
+ *                   harmonics lie in [-50, 50] and every offset lies in [-50, 50], the first point of every row of gene g; otherwise
+ *                   the row's default start, nu_0 = ln(sum_c wt k / sum_c wt e^logm), harmonics at their prior means or 0, delta = m
+ * With wt = (double)w_bc the sums of segment b are  sum (wt res) = dL/d delta_b,  h_b = sum (wt wo) B_i (W_b = h_b0),
+ * N with (wt wo)^2 + (wt res)^2,  L = sum wt term,  A = sum wt mag.  The priors of nu and delta are not weighted.  Each product with wt
+ * is formed first and is exact at wt == 1; the float64 operations that follow, the fold after each segment, the Schur complement with
+ * its cancellation-free row 0, the step and halving rules, the [-50, 50] bound, VC_GLM_ROUNDING over the K + Nb entries and the status
+ * codes are vc_gene_glm_batch's.  A batch whose cells all weigh 0 in a row is no error: D_b = q_b and its offset goes to its prior
+ * mean.  A row whose sum_c wt k is not a positive finite number (a NaN weight included) ends VC_GLM_UNBOUNDED with the outputs
+ * vc_gene_glm_batch gives a gene without counts: nu_0 as formed, harmonics 0, delta = m, cov_nu, delta_var, loglik and dec NaN,
+ * 0 iterations -- whatever the start holds.  Outputs, of row b and gene g at index b * Ng + g:
+ *   nu_dev double[R][Ng][K];  delta_dev double[R][Ng][Nb];
+ *   cov_nu_dev double[R][Ng][K (K + 1) / 2] and delta_var_dev double[R][Ng][Nb]: both NULL (not stored) or both given;
+ *   loglik_dev, dec_dev double[R][Ng];  iterations_dev, status_dev int32[R][Ng]
+ * Bits: identical under repetition; identical between uint16 and float32 storage; identical under any cutting of the genes or of the
+ * rows into calls (row b of an R-row call equals the call on that row alone); with a table of ones, R = 1 and no start all eight
+ * outputs equal vc_gene_glm_batch's on the same inputs bit for bit.  A (gene, row) pair's status touches no other pair's outputs; every
+ * path is bounded.  VC_ERR_ARG / VC_ERR_UNSUPPORTED as vc_gene_glm_batch's in its order (the two variance outputs may be NULL here),
+ * then weights_dev NULL, R outside 1..65535, weight_stride < Nc, one start pointer without the other, one variance pointer without
+ * the other: all decided before anything is launched.  Errors: vc_last_error(NULL). */
+int vc_gene_glm_batch_weighted(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* basis_dev,
+                               int K, const float* logm_dev, int noise, const float* r_dev, int Nb, const int64_t* seg_host,
+                               const double* delta_prior_mean_dev, const double* delta_prior_prec_dev, const double* prior_mean_dev,
+                               const double* prior_prec_dev, const float* weights_dev, int64_t R, int64_t weight_stride,
+                               const double* start_nu_dev, const double* start_delta_dev, double tol, int max_iter, double* nu_dev,
+                               double* delta_dev, double* cov_nu_dev, double* delta_var_dev, double* loglik_dev, double* dec_dev,
+                               int32_t* iterations_dev, int32_t* status_dev, void* hip_stream);
 
 /* --- per-gene negative-binomial dispersion given the means (stand-alone: no engine handle) -----------------------------------
  * The third factor of the model of vc_gene_glm: with eta_c = nu_g . basis[:, c] + logm[c], mu = exp(eta) known, maximise over

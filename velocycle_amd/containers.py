@@ -203,11 +203,18 @@ class Cycle(_HarmonicTable):
         `make_design_matrix` (or an integer label per cell); `delta_nu_prior`: (mean, std) of the offsets, scalars or
         [batches, genes].  `dispersion` is a number or one per gene ("mle" is refused).  Returns a Cycle, or with `return_fit=True`
         (Cycle, GeneBatchHarmonicFit): the fit holds `delta_nu` / `delta_nu_stds` [batches, genes], which
-        `Phases.from_cycle_batch_mle` consumes, and the likelihood-ratio statistic for periodicity given the batches."""
+        `Phases.from_cycle_batch_mle` consumes, and the likelihood-ratio statistic for periodicity given the batches.
+        `bootstrap=n > 0` (by name, default 0): the Cycle's stds are those of n cell bootstrap replicates
+        (`velocycle_amd.gene_bootstrap.gene_harmonics_batched_bootstrap`, seeded by `bootstrap_seed`, default 0) instead of the
+        Hessian's; the means are unchanged, and with `return_fit=True` the fit carries the `GeneBatchHarmonicBootstrap` (the
+        resampled offsets among it) as `fit.bootstrap`."""
         from .gene_batch import gene_harmonics_batched
         from .gene_harmonics import NOISEMODELS
         if noisemodel not in NOISEMODELS:
             raise NotImplementedError("Not implemented yet, sorry")
+        bootstrap, bootstrap_seed = worker_kw.pop("bootstrap", 0), worker_kw.pop("bootstrap_seed", 0)      # by name only
+        if int(bootstrap) != bootstrap or bootstrap < 0:
+            raise ValueError("bootstrap must be an integer >= 0 (the number of replicates)")
         if layer not in data.layers:
             raise ValueError(f"{layer=} is not a layer of the data")
         counts = data.layers[layer]
@@ -231,7 +238,17 @@ class Cycle(_HarmonicTable):
         fit = gene_harmonics_batched(counts, np.asarray(phases.phi_xy.values, dtype=np.float64), np.asarray(data.obs.n_scounts.values),
                                      batch_design, harmonics=harmonics, a=a, noisemodel=noisemodel, dispersion=dispersion,
                                      delta_nu_prior=delta_nu_prior, prior_means=prior_means, prior_stds=prior_stds, **worker_kw)
-        out = cls.from_array(fit.means, fit.stds, gene_names=data.var.index)
+        stds = fit.stds
+        if bootstrap:
+            from .gene_bootstrap import gene_harmonics_batched_bootstrap
+            run_kw = {k: worker_kw[k] for k in ("tol", "max_iter", "device", "chunk_genes", "storage") if k in worker_kw}
+            fit.bootstrap = gene_harmonics_batched_bootstrap(counts, np.asarray(phases.phi_xy.values, dtype=np.float64),
+                                                             np.asarray(data.obs.n_scounts.values), batch_design, harmonics=harmonics,
+                                                             a=a, noisemodel=noisemodel, dispersion=dispersion, n_boot=int(bootstrap),
+                                                             seed=bootstrap_seed, fit=fit, delta_nu_prior=delta_nu_prior,
+                                                             prior_means=prior_means, prior_stds=prior_stds, **run_kw)
+            stds = fit.bootstrap.stds
+        out = cls.from_array(fit.means, stds, gene_names=data.var.index)
         return (out, fit) if return_fit else out
 
 

@@ -14,7 +14,8 @@ batches.
 The cells are sorted by batch (a stable permutation of the basis, the offsets of eta and the staged block); staging, chunking and the
 lgamma constants are `gene_harmonics`' own.  The result does not depend on `chunk_genes`, uint16 / float32 storage, dense / CSR input or
 repetition bit for bit, and on the order of the cells only through the order of the sums.  `dispersion="mle"` is refused:
-`vc_gene_dispersion` does not know the offsets.  There is no CPU fallback."""
+`vc_gene_dispersion` does not know the offsets.  With `cell_weights=` the same fit runs under one row of case weights on
+`vc_gene_glm_batch_weighted`; `gene_bootstrap.gene_harmonics_batched_bootstrap` solves many rows per call.  There is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
@@ -24,7 +25,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gene_harmonics import GeneHarmonicFit, _check_run_options, _chunks, _constants, _open_device, _ptr, _unpack_tri, check_arguments
+from .gene_harmonics import (GeneHarmonicFit, _check_run_options, _chunks, _constants, _open_device, _ptr, _unpack_tri, check_arguments,
+                             check_weights)
 
 MAX_BATCHES = _lib.VC_GLM_MAX_BATCHES
 
@@ -45,6 +47,8 @@ class GeneBatchHarmonicFit:
     status: np.ndarray
     delta_nu: np.ndarray
     delta_nu_stds: np.ndarray
+
+    bootstrap = None                 # not a field: `Cycle.from_phases_batch_mle(bootstrap=n)` hangs its GeneBatchHarmonicBootstrap here
 
     harmonics = GeneHarmonicFit.harmonics
     lr_stat = GeneHarmonicFit.lr_stat
@@ -108,11 +112,20 @@ def batch_segments(labels, Nb):
 
 def gene_harmonics_batched(counts, directions, n_scounts, batches, harmonics=1, a=1, noisemodel="Poisson", dispersion=0.3, *,
                            delta_nu_prior=(0.0, 0.5), prior_means=None, prior_stds=None, tol=1e-10, max_iter=25, device=None,
-                           chunk_genes=None, storage="auto"):
+                           chunk_genes=None, storage="auto", **options):
     """counts, directions, n_scounts, harmonics, a, noisemodel, prior_means / prior_stds, tol, max_iter, device, chunk_genes, storage: as
     for `gene_harmonics`.  batches: a one-hot [Nc, Nb] design as `make_design_matrix` returns, or an integer label vector [Nc].
     delta_nu_prior: (mean, std) of the offsets, scalars or [Nb, Ng]; the defaults are the phase model's.  dispersion: a scalar or [Ng]
-    ("mle" is refused).  Returns a `GeneBatchHarmonicFit`."""
+    ("mle" is refused).  Returns a `GeneBatchHarmonicFit`.
+
+    cell_weights (accepted by name only, default None): [Nc] finite case weights >= 0 in the caller's cell order (float32 on the device).
+    Every cell's term of the log-likelihood, of its gradient and of its Hessian is multiplied by its weight, in the fit and in the null
+    model (K = 1 with offsets) alike, on `vc_gene_glm_batch_weighted` (one row, default start); the priors are not weighted; `loglik` and
+    `loglik_null` carry the weighted constants as `gene_harmonics`' do.  A vector of ones returns the unweighted result bit for bit.  A
+    batch whose cells all weigh 0 keeps its offset at the prior mean."""
+    cell_weights = options.pop("cell_weights", None)                                 # by name only: the signature is pinned
+    if options:
+        raise TypeError(f"gene_harmonics_batched() got unexpected keyword arguments {sorted(options)}")
     if isinstance(dispersion, str):
         if dispersion == "mle":
             raise ValueError("dispersion='mle' is not available with batches: vc_gene_dispersion does not know the batch offsets yet; "
@@ -122,6 +135,7 @@ def gene_harmonics_batched(counts, directions, n_scounts, batches, harmonics=1, 
                                              tol, max_iter)
     _check_run_options(storage, chunk_genes)
     Nc, Ng = int(counts.shape[0]), int(counts.shape[1])
+    w_host = check_weights(cell_weights, Nc, rows=1) if cell_weights is not None else None
     labels, Nb = batch_labels(batches, Nc)
     dm, dq = delta_prior(delta_nu_prior, Nb, Ng)
     perm, seg = batch_segments(labels, Nb)
@@ -132,6 +146,8 @@ def gene_harmonics_batched(counts, directions, n_scounts, batches, harmonics=1, 
     ptr = _ptr
     with torch.cuda.device(dev):
         perm_d = torch.from_numpy(perm).to(dev)
+        w_d = torch.from_numpy(w_host[:, perm]).to(dev).contiguous() if w_host is not None else None   # sorted like the cells
+        w64 = w_d[0].double() if w_d is not None else None
         B_d = basis[:, perm].to(torch.float32).to(dev).contiguous()
         logm_d = logm[perm].to(torch.float32).to(dev).contiguous()
         r_d = r.to(torch.float32).to(dev).contiguous() if r is not None else None
@@ -149,17 +165,20 @@ def gene_harmonics_batched(counts, directions, n_scounts, batches, harmonics=1, 
             same = kblk is blk
             blk = blk[:, perm_d].contiguous()                                        # cells of a batch contiguous, batches in order
             kblk = blk if same else kblk[:, perm_d].contiguous()
-            const[g0:g1] = _constants(blk, r64[g0:g1] if r64 is not None else None)
+            const[g0:g1] = _constants(blk, r64[g0:g1] if r64 is not None else None, w64)
             # the fit, then the constant with the offsets (K = 1: the null model, under the prior's nu0 column)
             for k_, outs, pm_c, pp_c in ((K, full, pm_d[g0:g1] if pm_d is not None else None, pp_d[g0:g1] if pp_d is not None else None),
                                          (1, null, pm_d[g0:g1, :1].contiguous() if pm_d is not None else None,
                                           pp_d[g0:g1, :1].contiguous() if pp_d is not None else None)):
-                rc = lib.vc_gene_glm_batch(ptr(kblk), kind, g1 - g0, Nc, Nc, ptr(B_d), k_, ptr(logm_d), _lib.NOISE[noisemodel],
-                                           ptr(r_d[g0:g1]) if r_d is not None else None, Nb, seg, ptr(dm_d[g0:g1]), ptr(dq_d[g0:g1]),
-                                           ptr(pm_c), ptr(pp_c), float(tol), int(max_iter),
-                                           *[ptr(outs[n][g0:g1]) for n in ("nu", "delta", "cov", "dvar", "ll", "dec", "it", "st")], stream)
+                head = (ptr(kblk), kind, g1 - g0, Nc, Nc, ptr(B_d), k_, ptr(logm_d), _lib.NOISE[noisemodel],
+                        ptr(r_d[g0:g1]) if r_d is not None else None, Nb, seg, ptr(dm_d[g0:g1]), ptr(dq_d[g0:g1]), ptr(pm_c), ptr(pp_c))
+                tail = (float(tol), int(max_iter), *[ptr(outs[n][g0:g1]) for n in ("nu", "delta", "cov", "dvar", "ll", "dec", "it", "st")], stream)
+                if w_d is not None:                                              # one row of case weights, each gene from its default start
+                    fn, rc = "vc_gene_glm_batch_weighted", lib.vc_gene_glm_batch_weighted(*head, ptr(w_d), 1, Nc, None, None, *tail)
+                else:
+                    fn, rc = "vc_gene_glm_batch", lib.vc_gene_glm_batch(*head, *tail)
                 if rc != _lib.VC_OK:
-                    raise HipEngineError(f"vc_gene_glm_batch failed ({rc}): {lib.vc_last_error(None).decode()}")
+                    raise HipEngineError(f"{fn} failed ({rc}): {lib.vc_last_error(None).decode()}")
             torch.cuda.current_stream(dev).synchronize()                             # the block and the slices outlive their launches
             del blk, kblk
         cov = _unpack_tri(full["cov"], K)

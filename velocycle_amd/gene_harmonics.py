@@ -401,8 +401,8 @@ def gene_harmonics(counts, directions, n_scounts, harmonics=1, a=1, noisemodel="
     gradient and of its Hessian is multiplied by its weight, in the fit and in the null model alike, on the kernel
     `vc_gene_glm_weighted` (one row of weights); `loglik` and `loglik_null` carry the weighted constants, `lr_stat` and `p_value` follow
     from them.  A vector of ones returns the unweighted result bit for bit.  A gene without a count in any cell of positive weight ends
-    UNBOUNDED.  `dispersion="mle"` with weights is refused: `vc_gene_dispersion` knows no weights (nor do the batch and kinetics
-    workers).  `gene_bootstrap.gene_harmonics_bootstrap` solves many rows of weights per call."""
+    UNBOUNDED.  `dispersion="mle"` with weights is refused: `vc_gene_dispersion` knows no weights (nor does the kinetics
+    worker; the batch worker has them: `gene_batch.gene_harmonics_batched(cell_weights=)`).  `gene_bootstrap.gene_harmonics_bootstrap` solves many rows of weights per call."""
     cell_weights = mle_options.pop("cell_weights", None)                             # by name only, like the options of "mle"
     if cell_weights is not None and isinstance(dispersion, str):
         raise ValueError("cell_weights with dispersion='mle' is not supported: vc_gene_dispersion knows no weights")
