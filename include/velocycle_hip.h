@@ -50,6 +50,9 @@
  *   vc_gene_kinetics            no counterpart (the reference learns logγg, logβg and νω only inside the SVI): the unspliced half of
  *                               velocity_inference_model.py:360-386 solved per gene for (log gamma, log beta) with the cycle, the
  *                               phases and the angular speed known, and the score and profile information of νω; stand-alone
+ *   vc_gene_kinetics_weighted   no counterpart: vc_gene_kinetics with case weights per cell, R rows of weights per call, each row at
+ *                               its own cycle, angular speed and start (the cell bootstrap of the kinetics fit and of the MAP
+ *                               angular speed); stand-alone, no engine
  *   vc_pca_stage, vc_pca_apply  Phases.from_pca_heuristic (phases.py:307-382): np.log(layer + small_count) and the one large
  *                               operation of a block power iteration that replaces sklearn's PCA(n_components).fit_transform
  *                               (:343-349); stand-alone, no engine
@@ -775,6 +778,47 @@ int vc_gene_kinetics(const void* counts_dev, int count_kind, int64_t Ng, int64_t
                      const float* r_dev, const double* prior_dev, const double* start_dev, double tol, int max_iter, double* xy_dev,
                      double* cov_dev, double* loglik_dev, double* dec_dev, int32_t* iterations_dev, int32_t* status_dev,
                      int32_t* n_clamped_dev, double* score_w_dev, double* info_w_dev, void* hip_stream);
+
+/* --- per-gene kinetics with case weights (stand-alone: no engine handle) --------------------------------------------------------
+ * vc_gene_kinetics with every cell's contribution multiplied by a weight w_bc >= 0, R rows of weights per call: the step
+ * vc_gene_glm_weighted takes from vc_gene_glm (the cell bootstrap of the kinetics fit and of the MAP angular speed; held-out fits).  One
+ * workgroup per (gene, row), grid (R, genes) with the row as the fast index, one launch per 65535 genes, no workspace, no allocation, no
+ * synchronisation; asynchronous on hip_stream.  counts_dev, count_kind, Ng, Nc, gene_stride, basis_dev, K, logm_dev, w_dev, NW, noise,
+ * r_dev, prior_dev, tol, max_iter: as for vc_gene_kinetics.  Every pointer is DEVICE memory.
+ *   weights_dev     float: w_bc at index b * weight_stride + c (weight_stride >= Nc; what lies between Nc and the stride is not read).
+ *                   Weights are taken to be finite and >= 0 (device memory is not read before the launch)
+ *   R               rows of weights, 1..65535 per call
+ * Per-row inputs, each with a stride in numbers from one row's table to the next; a stride of 0: one table shared by all rows.
+ *   nu_dev, nu_row_stride         double[Ng][K] (0), or double[R][Ng][K] (>= Ng K): a jointly resampled cycle
+ *   nuw_dev, nuw_row_stride       double[NW] (0), or double[R][NW] (>= NW): every replicate of an outer iteration at its own nuw
+ *   start_dev, start_row_stride   NULL, double[Ng][2] (0), or double[R][Ng][2] (>= 2 Ng): each row starts at its own (x, y)
+ * With wt = (double)w_bc every sum of a pass, of the default start's walk and of the profile pass takes its element times wt: res, w and
+ * wo of vc_gene_kinetics become wt res, wt w, wt wo in the gradient, both matrices, the score and the information; L = sum_c wt term
+ * (the negative binomial's r ln r is inside term and weighted with it), A = sum_c wt mag; the rounding scales are
+ * N_x = sum_c ((wt wo)^2 + (wt res)^2) p^2 and N_y = sum_c (wt wo)^2 + (wt res)^2; n_clamped counts the cells with w > 0 and z <= 0;
+ * the default start is x = mu_gamma, y = ln(sum_c wt e^etaS zp / sum_c wt k).  The priors are not weighted.  Each product with wt is
+ * formed first and is exact at wt == 1; the float64 operations that follow, the fold, the 2 x 2 algebra (observed where positive
+ * definite, else Fisher; the Fisher retry for a step out of the box; halving; the [-30, 30]^2 box; VC_KIN_ROUNDING; max_iter;
+ * max_iter == 0 -> VC_KIN_EVALUATED) and the status codes are vc_gene_kinetics'.  A row whose sum_c wt k is not a positive finite number
+ * (a NaN weight included) ends VC_KIN_NO_DATA with NaN outputs (iterations, n_clamped 0), whatever start_dev holds.
+ * Outputs, of row b and gene g at index b * Ng + g:
+ *   xy_dev double[R][Ng][2];  cov_dev NULL (not stored) or double[R][Ng][3];  loglik_dev, dec_dev double[R][Ng];
+ *   iterations_dev, status_dev, n_clamped_dev int32[R][Ng];  with NW > 0 score_w_dev double[R][Ng][NW] and
+ *   info_w_dev double[R][Ng][NW (NW + 1) / 2]
+ * Bits: identical under repetition; identical between uint16 and float32 storage; identical under any cutting of the genes or of the
+ * rows into calls (row b of an R-row call equals the call on that row alone, with that row's nu, nuw and start); with a table of ones,
+ * R = 1 and all strides 0 every one of the eleven outputs equals vc_gene_kinetics' on the same inputs bit for bit.  A (gene, row)
+ * pair's status touches no other pair's outputs; every path is bounded.  VC_ERR_ARG / VC_ERR_UNSUPPORTED as vc_gene_kinetics' in its
+ * order (cov_dev may be NULL here), then weights_dev NULL, R outside 1..65535, weight_stride < Nc, a non-zero stride smaller than one
+ * row's table (nu_row_stride < Ng K, nuw_row_stride < NW, start_row_stride < 2 Ng): all decided before anything is launched.
+ * Errors: vc_last_error(NULL). */
+int vc_gene_kinetics_weighted(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* basis_dev,
+                              int K, const float* logm_dev, const double* nu_dev, int64_t nu_row_stride, const float* w_dev, int NW,
+                              const double* nuw_dev, int64_t nuw_row_stride, int noise, const float* r_dev, const double* prior_dev,
+                              const float* weights_dev, int64_t R, int64_t weight_stride, const double* start_dev,
+                              int64_t start_row_stride, double tol, int max_iter, double* xy_dev, double* cov_dev, double* loglik_dev,
+                              double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, int32_t* n_clamped_dev, double* score_w_dev,
+                              double* info_w_dev, void* hip_stream);
 
 /* --- PCA phase prior (Phases.from_pca_heuristic, phases.py:307-382): staging and the power iteration's pass ------------------
  * Stand-alone (no engine); the iteration itself (QR, Rayleigh-Ritz on 8 x 8 matrices, float64) is the caller's:

@@ -300,8 +300,16 @@ class AngularSpeed(_HarmonicTable):
         [Nx, Nc] (None: one condition); prior: an `AngularSpeed` over the conditions (None: `trivial_prior`).  means = the mode, stds =
         sqrt of the diagonal of the inverse profile information (a Laplace standard error), both in this class's row layout.
         `return_fit=True` returns (AngularSpeed, VelocityMapFit); `fit.to_cycle(cycle)` is a copy of the cycle with `log_gammas` and
-        `log_betas` set.  Anything else goes to the worker (a, tol, max_iter, tol_outer, max_rounds, device, chunk_genes, storage, ...)."""
+        `log_betas` set.  Anything else goes to the worker (a, tol, max_iter, tol_outer, max_rounds, device, chunk_genes, storage, ...).
+        `bootstrap=n > 0` (by name, default 0): n cell bootstrap replicates of the fit
+        (`velocycle_amd.kinetics_bootstrap.velocity_map_bootstrap`, seeded by `bootstrap_seed`, default 0) are run as well and, with
+        `return_fit=True`, hang on the fit as `fit.bootstrap` (a `VelocityMapBootstrap`: `contrast_std(a, b)` is the standard error of
+        ln(ω_a / ω_b) whatever the noise model).  The returned means and stds are unchanged: the replicates carry sampling
+        variability and do not replace the Laplace width of an absolute ω."""
         from .gene_kinetics import NOISEMODELS, velocity_map
+        bootstrap, bootstrap_seed = worker_kw.pop("bootstrap", 0), worker_kw.pop("bootstrap_seed", 0)      # by name only
+        if isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, np.integer)) or bootstrap < 0:
+            raise ValueError("bootstrap must be an integer >= 0 (the number of replicates)")
         if noisemodel not in NOISEMODELS:
             raise NotImplementedError("Not implemented yet, sorry")
         if layer not in data.layers:
@@ -321,6 +329,13 @@ class AngularSpeed(_HarmonicTable):
         fit = velocity_map(counts, np.asarray(phases.phi_xy.values, dtype=np.float64), np.asarray(data.obs.n_scounts.values),
                            np.asarray(cycle.means.values, dtype=np.float64), harmonics_w=harmonics, condition_design=condition_design,
                            noisemodel=noisemodel, dispersion=dispersion, nuw_prior=prior, **worker_kw)
+        if bootstrap:
+            from .kinetics_bootstrap import velocity_map_bootstrap
+            fit.bootstrap = velocity_map_bootstrap(counts, np.asarray(phases.phi_xy.values, dtype=np.float64),
+                                                   np.asarray(data.obs.n_scounts.values), np.asarray(cycle.means.values, dtype=np.float64),
+                                                   harmonics_w=harmonics, condition_design=condition_design, noisemodel=noisemodel,
+                                                   dispersion=dispersion, n_boot=int(bootstrap), seed=bootstrap_seed, fit=fit,
+                                                   nuw_prior=prior, **worker_kw)
         rows = _row_labels(fit.nu_omega.shape[0], swapped=True)
         out = cls()
         out.means = pd.DataFrame(fit.nu_omega, index=rows, columns=names)

@@ -10,8 +10,12 @@ exponential (Bayesian bootstrap) weights or held-out fits (0 / 1).
 `gene_harmonics_batched_bootstrap` is the same for data pooled from several samples (`gene_batch.gene_harmonics_batched` /
 `Cycle.from_phases_batch_mle`) on `vc_gene_glm_batch_weighted`: every replicate estimates the harmonics and the per-batch offsets jointly.
 
-Limits: no weights in the dispersion (`dispersion="mle"`, `gene_dispersion`) or kinetics workers, and no `dispersion="mle"` with
-batches; no stratified resampling with fixed batch sizes (hand over a table); every row makes its own sweeps (one sweep does not serve
+The velocity half has its own module: `kinetics_bootstrap.velocity_map_bootstrap` resamples the MAP angular speed with the same draw
+(`draw_weights`: the same seed resamples the same cells) on `vc_gene_kinetics_weighted`, and takes this module's `replicates` as a
+jointly resampled cycle.
+
+Limits: no weights in the dispersion worker (`dispersion="mle"`, `gene_dispersion`), and no `dispersion="mle"` with batches; no batch
+offsets in the weighted kinetics; no stratified resampling with fixed batch sizes (hand over a table); every row makes its own sweeps (one sweep does not serve
 all R rows at the shared warm start); the cells are not sharded (one device holds a gene's row and the weight table); no Lognormal
 noise.  There is no CPU fallback."""
 from __future__ import annotations
