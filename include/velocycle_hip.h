@@ -820,6 +820,58 @@ int vc_gene_kinetics_weighted(const void* counts_dev, int count_kind, int64_t Ng
                               double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, int32_t* n_clamped_dev, double* score_w_dev,
                               double* info_w_dev, void* hip_stream);
 
+/* --- per-cell angular speed of the velocity model given the cycle, the phases and the kinetics (stand-alone: no engine handle) ---
+ * vc_gene_kinetics' model with the roles swapped: x_g = log gamma_g and y_g = log beta_g are given, and every cell's angular speed om_c
+ * is the one unknown of that cell's unspliced counts (local velocity; any group of cells is fitted by the caller from evaluate-only
+ * passes, whose sums add over cells).  Per cell c and gene g:
+ *   etaS = nu_g . basis[:, c] + logm[c],   d = sum_h h (nu_sin_h cos h phi - nu_cos_h sin h phi)     (as vc_gene_kinetics)
+ *   z = om_c d + e^x_g,   a = [z > 0],   zp = a z + 1e-5,   etaU = etaS - y_g + ln zp,   mu = e^(etaS - y_g) zp,   q = a d / zp
+ *   res = k - mu | (k - mu) r / (r + mu)     w = mu | mu r / (r + mu)     wo = mu | mu r (k + r) / (r + mu)^2     (Poisson | NB at r_g)
+ *   L_c(om) = sum_g  k etaU - mu  |  k etaU - (k + r) ln(r + mu) + r ln r
+ *   score_c = sum_g res q     fisher_c = sum_g w q^2     observed_c = sum_g (wo + res) q^2        (d2 etaU / d om2 = -q^2)
+ *   N_c = sum_g (wo^2 + res^2) q^2     A_c = sum_g |terms|     n_clamped_c = #{g : z <= 0}
+ *   f_c = L_c - (om - m_c)^2 / 2 s_c^2                                              (the optional Normal prior of the cell)
+ * One workgroup per 64 consecutive cells (lane = cell, the waves split the genes in a split that depends on Ng alone), one launch, no
+ * workspace, no allocation, no synchronisation; asynchronous on hip_stream.  Every pointer is DEVICE memory.  counts_dev (the UNSPLICED
+ * counts, dense [Ng][gene_stride], uint16 or float32), count_kind, Ng, Nc, gene_stride, basis_dev (float[K][Nc]), K in {3, 5},
+ * logm_dev, nu_dev, noise, r_dev: as for vc_gene_kinetics; Nc <= 2^31 - 1.
+ *   xy_dev          double[Ng][2]: log gamma, log beta of every gene
+ *   prior_dev       double[Nc][2]: mean and sd of the cell's Normal prior, or NULL: none
+ *   start_dev       double[Nc]: where every cell starts (required; a start outside [-30, 30] is moved to the nearer bound)
+ *   tol, max_iter   stop at the decrement G^2 / A <= tol (>= 0) after at most max_iter steps; max_iter == 0 evaluates at start_dev only
+ * Arithmetic as vc_gene_kinetics': etaS, d, z and etaS - y float64 from the float32 tables and the float64 parameters (the set of
+ * clamped genes is that of a float64 evaluation of the tables); e^(etaS - y) one float32 exp2 (vc_gene_glm's statements); res, w, wo,
+ * the NB logarithm and ln zp float32; every sum float64 in a fixed order, no atomics: identical bits under repetition, uint16 or
+ * float32 storage, any gene_stride, and any cutting of the cells into calls.  With G = score - (om - m) / s^2 a step is G / A, where
+ * A = observed + 1 / s^2 where that is positive, else fisher + 1 / s^2; om stays in [-30, 30].  Status per cell:
+ *   VC_CSP_CONVERGED  dec = G^2 / A <= tol
+ *   VC_CSP_ROUNDING   |G| <= 4 eps32 sqrt(N)
+ *   VC_CSP_MAX_ITER   max_iter steps were taken, the cell used up its 30 step halvings (a step is halved while f drops by more than
+ *                     8 eps32 max(A, A')), or the decrement is not finite
+ *   VC_CSP_UNBOUNDED  a full step would take om out of [-30, 30]; the last point inside is kept
+ *   VC_CSP_NO_DATA    the cell has no count, its start is not finite, or its prior is not finite (sd: or not > 0): every
+ *                     floating-point output NaN, iterations and n_clamped 0
+ *   VC_CSP_EVALUATED  max_iter == 0
+ * Outputs per cell, at the last accepted point:
+ *   omega_dev       double[Nc]
+ *   var_dev         double[Nc]: 1 / A of the A the decrement there was formed with
+ *   sums_dev        double[Nc][6]: L, score (without the prior term), fisher, observed, N, A
+ *   dec_dev double[Nc];  iterations_dev int32[Nc]: steps taken;  status_dev int32[Nc];  n_clamped_dev int32[Nc]
+ * A cell's status touches no other cell's outputs; every path is bounded (a workgroup makes at most max_iter + 31 passes).
+ * VC_ERR_ARG (NULL input or output, start_dev NULL, K not in {3, 5}, NB without r_dev, Nc < 1, Ng < 1, gene_stride < Nc, max_iter < 0,
+ * tol < 0), VC_ERR_UNSUPPORTED (Lognormal): all decided before anything is launched.  Errors: vc_last_error(NULL). */
+#define VC_CSP_CONVERGED 0
+#define VC_CSP_ROUNDING 1
+#define VC_CSP_MAX_ITER 2
+#define VC_CSP_UNBOUNDED 3
+#define VC_CSP_NO_DATA 4
+#define VC_CSP_EVALUATED 5
+int vc_cell_speed(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride, const float* basis_dev, int K,
+                  const float* logm_dev, const double* nu_dev, const double* xy_dev, int noise, const float* r_dev,
+                  const double* prior_dev, const double* start_dev, double tol, int max_iter, double* omega_dev, double* var_dev,
+                  double* sums_dev, double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, int32_t* n_clamped_dev,
+                  void* hip_stream);
+
 /* --- PCA phase prior (Phases.from_pca_heuristic, phases.py:307-382): staging and the power iteration's pass ------------------
  * Stand-alone (no engine); the iteration itself (QR, Rayleigh-Ritz on 8 x 8 matrices, float64) is the caller's:
  * velocycle_amd/phase_prior.py.  Both calls only enqueue on hip_stream.  Errors: vc_last_error(NULL).

@@ -9,7 +9,9 @@ __version__ = "0.1.0"
 # names served from their modules on first use (importing the package stays free of torch)
 _LAZY = {"gene_harmonics_bootstrap": "gene_bootstrap", "GeneHarmonicBootstrap": "gene_bootstrap",
          "gene_harmonics_batched_bootstrap": "gene_bootstrap", "GeneBatchHarmonicBootstrap": "gene_bootstrap",
-         "velocity_map_bootstrap": "kinetics_bootstrap", "VelocityMapBootstrap": "kinetics_bootstrap"}
+         "velocity_map_bootstrap": "kinetics_bootstrap", "VelocityMapBootstrap": "kinetics_bootstrap",
+         "cell_angular_speed": "cell_speed", "grouped_angular_speed": "cell_speed", "CellSpeedFit": "cell_speed",
+         "GroupSpeedFit": "cell_speed"}
 __all__ = sorted(_LAZY)
 
 
