@@ -53,6 +53,9 @@
  *   vc_gene_kinetics_weighted   no counterpart: vc_gene_kinetics with case weights per cell, R rows of weights per call, each row at
  *                               its own cycle, angular speed and start (the cell bootstrap of the kinetics fit and of the MAP
  *                               angular speed); stand-alone, no engine
+ *   vc_gene_joint               no counterpart (the deterministic side of the V-joint configuration): velocity_inference_model.py:
+ *                               360-386 solved per gene for (nu, log gamma, log beta) jointly from the spliced and the unspliced counts
+ *                               with the phases and the angular speed known, and the score and profile information of νω; stand-alone
  *   vc_pca_stage, vc_pca_apply  Phases.from_pca_heuristic (phases.py:307-382): np.log(layer + small_count) and the one large
  *                               operation of a block power iteration that replaces sklearn's PCA(n_components).fit_transform
  *                               (:343-349); stand-alone, no engine
@@ -871,6 +874,73 @@ int vc_cell_speed(const void* counts_dev, int count_kind, int64_t Ng, int64_t Nc
                   const double* prior_dev, const double* start_dev, double tol, int max_iter, double* omega_dev, double* var_dev,
                   double* sums_dev, double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, int32_t* n_clamped_dev,
                   void* hip_stream);
+
+/* --- joint per-gene fit of the harmonics and the kinetics over both layers (stand-alone: no engine handle) -----------------------
+ * velocity_inference_model.py:360-386 (with_delta_nu=False) with the phases and the angular speed known, solved per gene for
+ * theta = (nu [K], x = log gamma, y = log beta) from one row of spliced and one row of unspliced counts: vc_gene_glm and
+ * vc_gene_kinetics in one problem, in which nu also sees the unspliced layer (through etaS and through d inside the relu).  With
+ * b = basis[:, c], db its phi-derivative from the same rows (db_0 = 0, db_{2h-1} = h b_{2h}, db_{2h} = -h b_{2h-1}):
+ *   etaS = nu . b + logm[c],   d = nu . db,   om = sum_i nuw[i] w[i][c],   z = om d + e^x,   a = [z > 0],   zp = a z + 1e-5
+ *   etaU = etaS - y + ln zp,   muS = e^etaS,   muU = e^(etaS - y) zp
+ *   L_S, L_U = Poisson  sum_c k eta - mu     NB  sum_c k eta - (k + r) ln(r + mu) + Nc r ln r   (vc_gene_glm's convention; one r per gene)
+ *   f = L_S + L_U - (theta - m)' Lambda (theta - m) / 2     (Lambda diagonal: nu's from the two tables, x's and y's from prior_dev)
+ * One workgroup per gene, one launch, no workspace, no allocation, no synchronisation; asynchronous on hip_stream.  Every pointer is
+ * DEVICE memory.
+ *   counts_s_dev, counts_u_dev   the SPLICED and the UNSPLICED counts, each dense [Ng][gene_stride] of the same count_kind
+ *   count_kind, Ng, Nc, gene_stride, basis_dev, K, logm_dev, w_dev, NW, nuw_dev, noise, r_dev   as for vc_gene_kinetics (K in {3, 5},
+ *                   NW in 0..3, Nc <= 2^31 - 1)
+ *   prior_mean_dev, prior_prec_dev   double[Ng][K] each, as vc_gene_glm takes them, but REQUIRED here (without a prior on nu a gene with
+ *                   few cells has no maximum): every mean finite, every precision a positive finite number
+ *   prior_dev       double[Ng][4]: mu_gamma, sd_gamma, mu_beta, sd_beta (vc_gene_kinetics')
+ *   start_dev       double[Ng][K + 2] or NULL.  A gene whose start has an entry that is not finite or lies outside the box takes the
+ *                   default start, which is also NULL's: nu_0 = ln(sum_c k_S / sum_c e^logm), the harmonics at their prior means,
+ *                   x = mu_gamma, y = ln(sum_c e^etaS zp / sum_c k_U), clipped to the box
+ *   tol, max_iter   stop at the decrement G' A^-1 G <= tol (>= 0) after at most max_iter steps; max_iter == 0 evaluates at the start only
+ * Arithmetic as vc_gene_kinetics': etaS, d, om, z and etaS - y float64 from the float32 tables and the float64 parameters; e^etaS and
+ * e^(etaS - y) one float32 exp2 each; residuals, weights, the NB logarithm and ln zp float32; every sum float64 in a fixed order, the
+ * (K + 2)-dimensional algebra float64 (packed Cholesky).  With s = a om / zp, p = a e^x / zp, u = (s db, p, 0), gS = (b, 0, 0) and
+ * gU = (b + s db, p, -1):
+ *   G = sum_c resS gS + resU gU - Lambda (theta - m)
+ *   O = sum_c woS gS gS' + woU gU gU' + resU u u' - [sum_c resU p]_xx + Lambda     (observed)
+ *   F = sum_c wS gS gS' + wU gU gU' + Lambda                                       (Fisher, always positive definite)
+ *   N_i = sum_c (woS^2 + resS^2) gS_i^2 + (woU^2 + resU^2) gU_i^2                  (rounding scale of G_i)
+ * A step is A^-1 G with A = O where its Cholesky factorisation succeeds, else F (formed in a pass of its own, only then); nu stays
+ * in [-50, 50]^K, x and y in [-30, 30].  Status per gene (numbered like VC_KIN_*):
+ *   VC_JNT_CONVERGED  dec <= tol
+ *   VC_JNT_ROUNDING   every |G_i| <= 4 eps32 sqrt(N_i)
+ *   VC_JNT_MAX_ITER   max_iter steps were taken, the gene used up its 30 step halvings (a step is halved while f drops by more than
+ *                     8 eps32 max(sum |terms|, sum |terms|')), or the decrement is not finite
+ *   VC_JNT_UNBOUNDED  a full step would leave the box (one taken with O is first replaced by F's); the last point inside is kept
+ *   VC_JNT_NO_DATA    a prior, nuw or r is not finite (precision, sd, r: or not > 0), or a layer of the gene has no count: every
+ *                     floating-point output NaN, iterations and n_clamped 0
+ *   VC_JNT_EVALUATED  max_iter == 0
+ * Outputs per gene, at the last accepted point:
+ *   theta_dev       double[Ng][K + 2]: nu, x, y
+ *   cov_dev         double[Ng][(K + 2)(K + 3) / 2]: A^-1 of the matrix A the decrement there was formed with, lower triangle packed
+ *                   row by row like vc_gene_glm's
+ *   loglik_s_dev, loglik_u_dev   double[Ng]: L_S and L_U, without the prior terms;  dec_dev double[Ng]
+ *   iterations_dev int32[Ng]: steps taken;  status_dev int32[Ng];  n_clamped_dev int32[Ng]: the number of cells with z <= 0
+ *   score_w_dev     double[Ng][NW]: sum_c resU q w[i][c], q = a d / zp (NW > 0)
+ *   info_w_dev      double[Ng][NW (NW + 1) / 2]: I_ww - I_wt (I_tt + Lambda)^-1 I_tw with I the Fisher information over
+ *                   (q w[.][c], gU) for the unspliced plus gS for the spliced layer, t = all K + 2 parameters (NW > 0; one further pass)
+ * Bits: identical under repetition, uint16 or float32 storage, any gene_stride and any cutting of the genes into calls; at
+ * max_iter == 0 loglik_u_dev and n_clamped_dev equal vc_gene_kinetics' evaluate-only outputs at the same (nu, x, y, w, nuw).  A gene's
+ * status touches no other gene's outputs; every path is bounded.  VC_ERR_ARG (NULL input or output, the nu prior tables included; K
+ * not in {3, 5}; NW outside 0..3; NW > 0 without w_dev, nuw_dev, score_w_dev or info_w_dev; score_w_dev or info_w_dev with NW == 0; NB
+ * without r_dev; Nc < 1, Ng < 1, gene_stride < Nc, max_iter < 0, max_iter == 0 without start_dev, tol < 0), VC_ERR_UNSUPPORTED
+ * (Lognormal): all decided before anything is launched.  Errors: vc_last_error(NULL). */
+#define VC_JNT_CONVERGED 0
+#define VC_JNT_ROUNDING 1
+#define VC_JNT_MAX_ITER 2
+#define VC_JNT_UNBOUNDED 3
+#define VC_JNT_NO_DATA 4
+#define VC_JNT_EVALUATED 5
+int vc_gene_joint(const void* counts_s_dev, const void* counts_u_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride,
+                  const float* basis_dev, int K, const float* logm_dev, const float* w_dev, int NW, const double* nuw_dev, int noise,
+                  const float* r_dev, const double* prior_mean_dev, const double* prior_prec_dev, const double* prior_dev,
+                  const double* start_dev, double tol, int max_iter, double* theta_dev, double* cov_dev, double* loglik_s_dev,
+                  double* loglik_u_dev, double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, int32_t* n_clamped_dev,
+                  double* score_w_dev, double* info_w_dev, void* hip_stream);
 
 /* --- PCA phase prior (Phases.from_pca_heuristic, phases.py:307-382): staging and the power iteration's pass ------------------
  * Stand-alone (no engine); the iteration itself (QR, Rayleigh-Ritz on 8 x 8 matrices, float64) is the caller's:

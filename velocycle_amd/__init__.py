@@ -11,7 +11,8 @@ _LAZY = {"gene_harmonics_bootstrap": "gene_bootstrap", "GeneHarmonicBootstrap": 
          "gene_harmonics_batched_bootstrap": "gene_bootstrap", "GeneBatchHarmonicBootstrap": "gene_bootstrap",
          "velocity_map_bootstrap": "kinetics_bootstrap", "VelocityMapBootstrap": "kinetics_bootstrap",
          "cell_angular_speed": "cell_speed", "grouped_angular_speed": "cell_speed", "CellSpeedFit": "cell_speed",
-         "GroupSpeedFit": "cell_speed"}
+         "GroupSpeedFit": "cell_speed", "velocity_map_joint": "gene_joint", "GeneJointFit": "gene_joint",
+         "JointVelocityMapFit": "gene_joint"}            # (`gene_joint` itself is its module's name: velocycle_amd.gene_joint.gene_joint)
 __all__ = sorted(_LAZY)
 
 

@@ -27,6 +27,7 @@ VC_GLM_MAX_BATCHES = 32
 VC_DISP_CONVERGED, VC_DISP_ROUNDING, VC_DISP_AT_UPPER, VC_DISP_AT_LOWER, VC_DISP_MAX_ITER, VC_DISP_EVALUATED, VC_DISP_NO_DATA = range(7)
 VC_KIN_CONVERGED, VC_KIN_ROUNDING, VC_KIN_MAX_ITER, VC_KIN_UNBOUNDED, VC_KIN_NO_DATA, VC_KIN_EVALUATED = range(6)
 VC_CSP_CONVERGED, VC_CSP_ROUNDING, VC_CSP_MAX_ITER, VC_CSP_UNBOUNDED, VC_CSP_NO_DATA, VC_CSP_EVALUATED = range(6)
+VC_JNT_CONVERGED, VC_JNT_ROUNDING, VC_JNT_MAX_ITER, VC_JNT_UNBOUNDED, VC_JNT_NO_DATA, VC_JNT_EVALUATED = range(6)
 VC_DISP_RHO_MIN, VC_DISP_RHO_MAX =-6.907755278982137, 13.815510557964274           # ln 1e-3, ln 1e6
 
 # sample sites, parameters and eps blocks, named as in the reference
@@ -166,6 +167,10 @@ EXPORTS = {
     "vc_cell_speed": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vc_gene_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
     "vc_pca_stage": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p]),
     "vc_pca_apply_workspace": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),

@@ -195,6 +195,28 @@ class Cycle(_HarmonicTable):
         return (out, fit) if return_fit else out
 
     @classmethod
+    def from_joint_mle(cls, phases, data, angular_speed, harmonics=1, condition_design=None, a=1, noisemodel='Poisson', dispersion=0.3, *,
+                       prior=None, return_fit=False, **worker_kw):
+        """The cycle AND the kinetics of every gene given the cells' `phases` and an `angular_speed` (an `AngularSpeed`, or a scalar or
+        one value per cell), fitted jointly to the `spliced` and `unspliced` layers by the HIP kernel behind
+        `velocycle_amd.gene_joint.gene_joint` (the V-joint configuration; reference velocity_inference_model.py:360-386,
+        with_delta_nu=False).  means / stds = the modes of ν and their Laplace standard errors, `log_gammas` and `log_betas` are set.
+        prior: a Cycle over the same genes and harmonics (None: Normal(0, 3)).  `return_fit=True` returns (Cycle, GeneJointFit);
+        anything else goes to the worker (kinetics_prior, start, tol, max_iter, device, chunk_genes, storage)."""
+        from .gene_joint import gene_joint
+        counts_S, counts_U, xy, n, prior_means, prior_stds = _joint_inputs(phases, data, harmonics, noisemodel, prior)
+        if isinstance(angular_speed, AngularSpeed):
+            Hw = (angular_speed.means.shape[0] - 1) // 2
+            speed = dict(nu_omega=np.ascontiguousarray(np.asarray(angular_speed.means.values, dtype=np.float64).T).reshape(-1),
+                         harmonics_w=Hw, condition_design=condition_design)
+        else:
+            speed = dict(omega=angular_speed)
+        fit = gene_joint(counts_S, counts_U, xy, n, harmonics=harmonics, a=a, noisemodel=noisemodel, dispersion=dispersion,
+                         prior_means=prior_means, prior_stds=prior_stds, **speed, **worker_kw)
+        out = fit.to_cycle(list(data.var.index))
+        return (out, fit) if return_fit else out
+
+    @classmethod
     def from_phases_batch_mle(cls, phases, data, batch_design, harmonics=1, a=1, noisemodel='Poisson', dispersion=0.3, *,
                               layer='spliced', delta_nu_prior=(0.0, 0.5), prior=None, return_fit=False, **worker_kw):
         """`from_phases_mle` for data pooled from several samples: the phase model's per-batch offsets (ElogS = nu . zeta(phi) +
@@ -341,6 +363,56 @@ class AngularSpeed(_HarmonicTable):
         out.means = pd.DataFrame(fit.nu_omega, index=rows, columns=names)
         out.stds = pd.DataFrame(fit.stds, index=rows, columns=names)
         return (out, fit) if return_fit else out
+
+    @classmethod
+    def from_joint_mle(cls, cycle_prior, phases, data, harmonics=0, condition_design=None, noisemodel='Poisson', dispersion=0.3, *,
+                       cycle_harmonics=1, prior=None, return_fit=False, **worker_kw):
+        """The MAP angular speed of the V-joint configuration: conditioned on the `phases` only, with every gene's ν, log γ and log β
+        profiled out over the `spliced` and `unspliced` layers under their priors, by the HIP kernel behind
+        `velocycle_amd.gene_joint.velocity_map_joint`.  cycle_prior: a Cycle over the same genes whose means and stds are ν's prior
+        (None: Normal(0, 3) at `cycle_harmonics` harmonics); harmonics: Hω; condition_design: [Nx, Nc] (None: one condition); prior:
+        an `AngularSpeed` over the conditions (None: `trivial_prior`).  `return_fit=True` returns (AngularSpeed, JointVelocityMapFit);
+        `fit.to_cycle(gene_names)` is the jointly fitted Cycle.  Anything else goes to the worker (a, kinetics_prior, start, tol,
+        max_iter, tol_outer, max_rounds, device, chunk_genes, storage)."""
+        from .gene_joint import velocity_map_joint
+        H = cycle_prior.harmonics if cycle_prior is not None else cycle_harmonics
+        counts_S, counts_U, xy, n, prior_means, prior_stds = _joint_inputs(phases, data, H, noisemodel, cycle_prior)
+        Nx = 1 if condition_design is None else int(np.asarray(condition_design).shape[0])
+        names = list(prior.means.columns) if prior is not None else list(range(Nx))
+        fit = velocity_map_joint(counts_S, counts_U, xy, n, harmonics=H, harmonics_w=harmonics, condition_design=condition_design,
+                                 noisemodel=noisemodel, dispersion=dispersion, prior_means=prior_means, prior_stds=prior_stds,
+                                 nuw_prior=prior, **worker_kw)
+        rows = _row_labels(fit.nu_omega.shape[0], swapped=True)
+        out = cls()
+        out.means = pd.DataFrame(fit.nu_omega, index=rows, columns=names)
+        out.stds = pd.DataFrame(fit.stds, index=rows, columns=names)
+        return (out, fit) if return_fit else out
+
+
+def _joint_inputs(phases, data, harmonics, noisemodel, prior):
+    """What `Cycle.from_joint_mle` and `AngularSpeed.from_joint_mle` read from their containers: (spliced, unspliced, directions,
+    n_scounts, prior means, prior stds), refused as `from_phases_mle` / `from_kinetics_mle` refuse."""
+    if noisemodel not in ("Poisson", "NegativeBinomial"):
+        raise NotImplementedError("Not implemented yet, sorry")
+    for layer in ("spliced", "unspliced"):
+        if layer not in data.layers:
+            raise ValueError(f"{layer=} is not a layer of the data")
+    counts = [data.layers["spliced"], data.layers["unspliced"]]
+    Nc, Ng = counts[0].shape
+    named = not isinstance(phases.phi_xy.columns, pd.RangeIndex)
+    if phases.phi_xy.shape[1] != Nc or (named and list(phases.phi_xy.columns) != list(data.obs.index)):
+        raise ValueError("the cells of the phases do not match the cells of the data (same cells, same order)")
+    prior_means = prior_stds = None
+    if prior is not None:
+        named = not isinstance(prior.means.columns, pd.RangeIndex)
+        if prior.means.shape[1] != Ng or (named and list(prior.means.columns) != list(data.var.index)):
+            raise ValueError("the genes of the prior do not match the genes of the data (same genes, same order)")
+        if prior.harmonics != harmonics:
+            raise ValueError(f"the prior has {prior.harmonics} harmonics, the fit {harmonics}")
+        prior_means = np.asarray(prior.means.values, dtype=np.float64)
+        prior_stds = np.asarray(prior.stds.values, dtype=np.float64)
+    counts = [c if (hasattr(c, "tocsr") or torch.is_tensor(c)) else np.asarray(c) for c in counts]
+    return counts[0], counts[1], np.asarray(phases.phi_xy.values, dtype=np.float64), np.asarray(data.obs.n_scounts.values), prior_means, prior_stds
 
 
 class Phases:
