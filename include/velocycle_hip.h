@@ -56,6 +56,9 @@
  *   vc_gene_joint               no counterpart (the deterministic side of the V-joint configuration): velocity_inference_model.py:
  *                               360-386 solved per gene for (nu, log gamma, log beta) jointly from the spliced and the unspliced counts
  *                               with the phases and the angular speed known, and the score and profile information of νω; stand-alone
+ *   vc_gene_joint_weighted      no counterpart: vc_gene_joint with case weights per cell, R rows of weights per call, each row at its
+ *                               own angular speed and start (the cell bootstrap of the joint fit and of its MAP angular speed);
+ *                               stand-alone, no engine
  *   vc_pca_stage, vc_pca_apply  Phases.from_pca_heuristic (phases.py:307-382): np.log(layer + small_count) and the one large
  *                               operation of a block power iteration that replaces sklearn's PCA(n_components).fit_transform
  *                               (:343-349); stand-alone, no engine
@@ -941,6 +944,50 @@ int vc_gene_joint(const void* counts_s_dev, const void* counts_u_dev, int count_
                   const double* start_dev, double tol, int max_iter, double* theta_dev, double* cov_dev, double* loglik_s_dev,
                   double* loglik_u_dev, double* dec_dev, int32_t* iterations_dev, int32_t* status_dev, int32_t* n_clamped_dev,
                   double* score_w_dev, double* info_w_dev, void* hip_stream);
+
+/* --- joint per-gene fit with case weights (stand-alone: no engine handle) ---------------------------------------------------------
+ * vc_gene_joint with every cell's contribution multiplied by a weight w_bc >= 0, R rows of weights per call: the step
+ * vc_gene_kinetics_weighted takes from vc_gene_kinetics (the cell bootstrap of the joint fit and of its MAP angular speed; held-out
+ * fits).  One workgroup per (gene, row), grid (R, genes) with the row as the fast index, one launch per 65535 genes, no workspace, no
+ * allocation, no synchronisation; asynchronous on hip_stream.  counts_s_dev, counts_u_dev, count_kind, Ng, Nc, gene_stride, basis_dev,
+ * K, logm_dev, w_dev, NW, noise, r_dev, prior_mean_dev, prior_prec_dev, prior_dev, tol, max_iter: as for vc_gene_joint (the priors are
+ * shared by the rows and are not weighted; there is no nu table: nu is an unknown here).  Every pointer is DEVICE memory.
+ *   weights_dev     float: w_bc at index b * weight_stride + c (weight_stride >= Nc; what lies between Nc and the stride is not read).
+ *                   Weights are taken to be finite and >= 0 (device memory is not read before the launch)
+ *   R               rows of weights, 1..65535 per call
+ * Per-row inputs, each with a stride in numbers from one row's table to the next; a stride of 0: one table shared by all rows.
+ *   nuw_dev, nuw_row_stride       double[NW] (0), or double[R][NW] (>= NW): every replicate of an outer iteration at its own nuw
+ *   start_dev, start_row_stride   NULL, double[Ng][K + 2] (0), or double[R][Ng][K + 2] (>= Ng (K + 2)): each row starts at its own theta
+ *                                 (a pair whose start has an entry that is not finite or lies outside the box takes the default start)
+ * With wt = (double)w_bc every sum of a regular pass, of the Fisher pass, of the default start's walk and of the profile pass takes its
+ * element times wt: res, w and wo of both layers become wt res, wt w, wt wo in G, O, F, the score and the information; L_S and L_U are
+ * sum_c wt term (the negative binomial's r ln r is inside term and weighted with it); the halving allowance uses A = sum_c wt |terms|;
+ * the rounding scales are N_i = sum_c ((wt woS)^2 + (wt resS)^2) gS_i^2 + ((wt woU)^2 + (wt resU)^2) gU_i^2; n_clamped counts the
+ * cells with w > 0 and z <= 0; the default start is nu_0 = ln(sum_c wt k_S / sum_c wt e^logm), y = ln(sum_c wt e^etaS zp / sum_c wt k_U).
+ * Each product with wt is formed first and is exact at wt == 1; the float64 operations that follow, the fold, the packed Cholesky
+ * algebra (observed where its factorisation succeeds, else Fisher from a pass of its own; the Fisher retry for a step out of the box;
+ * halving; the boxes; VC_JNT_ROUNDING; max_iter; max_iter == 0 -> VC_JNT_EVALUATED) and the status codes are vc_gene_joint's.  A
+ * (gene, row) pair whose sum_c wt k_S or sum_c wt k_U is not a positive finite number (a NaN weight included) ends VC_JNT_NO_DATA with
+ * NaN outputs (iterations, n_clamped 0), whatever start_dev holds.
+ * Outputs, of row b and gene g at index b * Ng + g:
+ *   theta_dev double[R][Ng][K + 2];  cov_dev NULL (not stored) or double[R][Ng][(K + 2)(K + 3) / 2];
+ *   loglik_s_dev, loglik_u_dev, dec_dev double[R][Ng];  iterations_dev, status_dev, n_clamped_dev int32[R][Ng];
+ *   with NW > 0 score_w_dev double[R][Ng][NW] and info_w_dev double[R][Ng][NW (NW + 1) / 2]
+ * Bits: identical under repetition; identical between uint16 and float32 storage; identical under any gene_stride and weight_stride and
+ * any cutting of the genes or of the rows into calls (row b of an R-row call equals the call on that row alone, with that row's nuw and
+ * start); with a table of ones, R = 1 and all strides 0 every one of vc_gene_joint's outputs is reproduced bit for bit.  A (gene, row)
+ * pair's status touches no other pair's outputs; every path is bounded.  VC_ERR_ARG / VC_ERR_UNSUPPORTED as vc_gene_joint's in its
+ * order (cov_dev may be NULL here), then weights_dev NULL, R outside 1..65535, weight_stride < Nc, a non-zero stride smaller than one
+ * row's table (nuw_row_stride < NW, start_row_stride < Ng (K + 2)): all decided before anything is launched.
+ * Errors: vc_last_error(NULL). */
+int vc_gene_joint_weighted(const void* counts_s_dev, const void* counts_u_dev, int count_kind, int64_t Ng, int64_t Nc, int64_t gene_stride,
+                           const float* basis_dev, int K, const float* logm_dev, const float* w_dev, int NW, const double* nuw_dev,
+                           int64_t nuw_row_stride, int noise, const float* r_dev, const double* prior_mean_dev,
+                           const double* prior_prec_dev, const double* prior_dev, const float* weights_dev, int64_t R,
+                           int64_t weight_stride, const double* start_dev, int64_t start_row_stride, double tol, int max_iter,
+                           double* theta_dev, double* cov_dev, double* loglik_s_dev, double* loglik_u_dev, double* dec_dev,
+                           int32_t* iterations_dev, int32_t* status_dev, int32_t* n_clamped_dev, double* score_w_dev, double* info_w_dev,
+                           void* hip_stream);
 
 /* --- PCA phase prior (Phases.from_pca_heuristic, phases.py:307-382): staging and the power iteration's pass ------------------
  * Stand-alone (no engine); the iteration itself (QR, Rayleigh-Ritz on 8 x 8 matrices, float64) is the caller's:

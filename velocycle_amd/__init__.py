@@ -12,7 +12,9 @@ _LAZY = {"gene_harmonics_bootstrap": "gene_bootstrap", "GeneHarmonicBootstrap": 
          "velocity_map_bootstrap": "kinetics_bootstrap", "VelocityMapBootstrap": "kinetics_bootstrap",
          "cell_angular_speed": "cell_speed", "grouped_angular_speed": "cell_speed", "CellSpeedFit": "cell_speed",
          "GroupSpeedFit": "cell_speed", "velocity_map_joint": "gene_joint", "GeneJointFit": "gene_joint",
-         "JointVelocityMapFit": "gene_joint"}            # (`gene_joint` itself is its module's name: velocycle_amd.gene_joint.gene_joint)
+         "JointVelocityMapFit": "gene_joint",            # (`gene_joint` itself is its module's name: velocycle_amd.gene_joint.gene_joint)
+         "gene_joint_weighted": "joint_bootstrap", "gene_joint_bootstrap": "joint_bootstrap", "GeneJointBootstrap": "joint_bootstrap",
+         "velocity_map_joint_bootstrap": "joint_bootstrap", "JointVelocityMapBootstrap": "joint_bootstrap"}
 __all__ = sorted(_LAZY)
 
 

@@ -202,8 +202,15 @@ class Cycle(_HarmonicTable):
         `velocycle_amd.gene_joint.gene_joint` (the V-joint configuration; reference velocity_inference_model.py:360-386,
         with_delta_nu=False).  means / stds = the modes of ν and their Laplace standard errors, `log_gammas` and `log_betas` are set.
         prior: a Cycle over the same genes and harmonics (None: Normal(0, 3)).  `return_fit=True` returns (Cycle, GeneJointFit);
-        anything else goes to the worker (kinetics_prior, start, tol, max_iter, device, chunk_genes, storage)."""
+        anything else goes to the worker (kinetics_prior, start, tol, max_iter, device, chunk_genes, storage).
+        `bootstrap=n > 0` (by name, default 0): the Cycle's stds are those of n cell bootstrap replicates of the joint fit
+        (`velocycle_amd.joint_bootstrap.gene_joint_bootstrap`, seeded by `bootstrap_seed`, default 0: `gene_stds()`) instead of
+        Laplace's; the means and the kinetics are unchanged, and with `return_fit=True` the fit carries the `GeneJointBootstrap` as
+        `fit.bootstrap`.  Those replicates hold `angular_speed` FIXED at what was handed over: the stds leave out what the uncertainty
+        of ω adds to ν, log γ and log β.  For stds that resample ω with the genes use `AngularSpeed.from_joint_mle(..., bootstrap=n,
+        return_fit=True)` and `fit.bootstrap.to_cycle(gene_names)`."""
         from .gene_joint import gene_joint
+        bootstrap, bootstrap_seed = _bootstrap_options(worker_kw)
         counts_S, counts_U, xy, n, prior_means, prior_stds = _joint_inputs(phases, data, harmonics, noisemodel, prior)
         if isinstance(angular_speed, AngularSpeed):
             Hw = (angular_speed.means.shape[0] - 1) // 2
@@ -214,6 +221,13 @@ class Cycle(_HarmonicTable):
         fit = gene_joint(counts_S, counts_U, xy, n, harmonics=harmonics, a=a, noisemodel=noisemodel, dispersion=dispersion,
                          prior_means=prior_means, prior_stds=prior_stds, **speed, **worker_kw)
         out = fit.to_cycle(list(data.var.index))
+        if bootstrap:
+            from .joint_bootstrap import gene_joint_bootstrap
+            run_kw = {k: worker_kw[k] for k in ("kinetics_prior", "tol", "max_iter", "device", "chunk_genes", "storage") if k in worker_kw}
+            fit.bootstrap = gene_joint_bootstrap(counts_S, counts_U, xy, n, harmonics=harmonics, a=a, noisemodel=noisemodel,
+                                                 dispersion=dispersion, n_boot=int(bootstrap), seed=bootstrap_seed, fit=fit,
+                                                 prior_means=prior_means, prior_stds=prior_stds, **speed, **run_kw)
+            out = fit.bootstrap.to_cycle(list(data.var.index))
         return (out, fit) if return_fit else out
 
     @classmethod
@@ -373,8 +387,14 @@ class AngularSpeed(_HarmonicTable):
         (None: Normal(0, 3) at `cycle_harmonics` harmonics); harmonics: Hω; condition_design: [Nx, Nc] (None: one condition); prior:
         an `AngularSpeed` over the conditions (None: `trivial_prior`).  `return_fit=True` returns (AngularSpeed, JointVelocityMapFit);
         `fit.to_cycle(gene_names)` is the jointly fitted Cycle.  Anything else goes to the worker (a, kinetics_prior, start, tol,
-        max_iter, tol_outer, max_rounds, device, chunk_genes, storage)."""
+        max_iter, tol_outer, max_rounds, device, chunk_genes, storage).
+        `bootstrap=n > 0` (by name, default 0): n cell bootstrap replicates of the fit
+        (`velocycle_amd.joint_bootstrap.velocity_map_joint_bootstrap`, seeded by `bootstrap_seed`, default 0, genes kept) are run as
+        well and, with `return_fit=True`, hang on the fit as `fit.bootstrap` (a `JointVelocityMapBootstrap`: `contrast_std(a, b)` is the
+        standard error of ln(ω_a / ω_b) whatever the noise model; `to_cycle` the joint cycle with bootstrap stds).  The returned means
+        and stds are unchanged: the replicates carry sampling variability and do not replace the Laplace width of an absolute ω."""
         from .gene_joint import velocity_map_joint
+        bootstrap, bootstrap_seed = _bootstrap_options(worker_kw)
         H = cycle_prior.harmonics if cycle_prior is not None else cycle_harmonics
         counts_S, counts_U, xy, n, prior_means, prior_stds = _joint_inputs(phases, data, H, noisemodel, cycle_prior)
         Nx = 1 if condition_design is None else int(np.asarray(condition_design).shape[0])
@@ -382,11 +402,28 @@ class AngularSpeed(_HarmonicTable):
         fit = velocity_map_joint(counts_S, counts_U, xy, n, harmonics=H, harmonics_w=harmonics, condition_design=condition_design,
                                  noisemodel=noisemodel, dispersion=dispersion, prior_means=prior_means, prior_stds=prior_stds,
                                  nuw_prior=prior, **worker_kw)
+        if bootstrap:
+            from .joint_bootstrap import velocity_map_joint_bootstrap
+            run_kw = {k: v for k, v in worker_kw.items() if k != "start"}          # the replicates start at the fit
+            fit.bootstrap = velocity_map_joint_bootstrap(counts_S, counts_U, xy, n, harmonics=H, harmonics_w=harmonics,
+                                                         condition_design=condition_design, noisemodel=noisemodel, dispersion=dispersion,
+                                                         n_boot=int(bootstrap), seed=bootstrap_seed, fit=fit, keep_genes=True,
+                                                         prior_means=prior_means, prior_stds=prior_stds, nuw_prior=prior, **run_kw)
         rows = _row_labels(fit.nu_omega.shape[0], swapped=True)
         out = cls()
         out.means = pd.DataFrame(fit.nu_omega, index=rows, columns=names)
         out.stds = pd.DataFrame(fit.stds, index=rows, columns=names)
         return (out, fit) if return_fit else out
+
+
+def _bootstrap_options(worker_kw):
+    """(bootstrap, bootstrap_seed) taken out of a worker's keywords: by name only, default 0."""
+    bootstrap, bootstrap_seed = worker_kw.pop("bootstrap", 0), worker_kw.pop("bootstrap_seed", 0)
+    if isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, np.integer)) or bootstrap < 0:
+        raise ValueError("bootstrap must be an integer >= 0 (the number of replicates)")
+    if isinstance(bootstrap_seed, bool) or not isinstance(bootstrap_seed, (int, np.integer)) or bootstrap_seed < 0:
+        raise ValueError("bootstrap_seed must be an integer >= 0")
+    return int(bootstrap), int(bootstrap_seed)
 
 
 def _joint_inputs(phases, data, harmonics, noisemodel, prior):

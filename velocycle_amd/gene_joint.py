@@ -16,8 +16,8 @@ in `gene_kinetics.velocity_map`, by a damped Newton iteration over the kernel's 
 of νω) are conditioned on; the standard errors are Laplace's at the mode; `relu` is the model's, kink included (`n_clamped`).
 
 Genes are independent: both layers are staged in the same chunks, and the result does not depend on the chunk size or the storage
-bit for bit.  Cells cannot be cut.  Not here: Δν, H = 3, more than 3 coefficients of νω, Lognormal noise, case weights.  There is no
-CPU fallback.
+bit for bit.  Cells cannot be cut.  Not here: Δν, H = 3, more than 3 coefficients of νω, Lognormal noise; case weights and the cell
+bootstrap are `joint_bootstrap`'s (`gene_joint_weighted`, `velocity_map_joint_bootstrap`).  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -62,6 +62,7 @@ class GeneJointFit:
     n_clamped: np.ndarray
     score_w: np.ndarray
     info_w: np.ndarray
+    bootstrap = None                 # `Cycle.from_joint_mle(bootstrap=n)` hangs its GeneJointBootstrap here: an attribute, not a field
 
     def to_cycle(self, cycle_or_gene_names):
         """A `Cycle` with means, stds, `log_gammas` and `log_betas` set: a copy of the given cycle, or a new one over the gene names."""
@@ -96,6 +97,7 @@ class JointVelocityMapFit:
     n_excluded: int
     included: np.ndarray
     genes: GeneJointFit
+    bootstrap = None                 # `AngularSpeed.from_joint_mle(bootstrap=n)` hangs its JointVelocityMapBootstrap here: an attribute, not a field
 
     def to_cycle(self, cycle_or_gene_names):
         return self.genes.to_cycle(cycle_or_gene_names)
