@@ -1,6 +1,6 @@
 """GPU: the five engine-less entry points of include/velocycle_hip.h -- vc_gene_glm, vc_gene_glm_batch, vc_gene_dispersion,
 vc_gene_kinetics, vc_phase_mle -- called directly in every layout their header allows (tests/cabi_layouts.py; what the layouts are is
-checked without a device in tests/test_cabi_layouts_cpu.py).
+checked without a device in tests/test_cabi_layouts_cpu.py).  The six later entry points: tests/test_hip_cabi_layouts_six.py.
 
 Anchor: the `compact` direct call (gene_stride == Nc, the workers' convention) is held to the float64 checker at the standing bars of
 that kernel's own GPU test file, through that file's judging helper, and equals the Python worker bit for bit on every output the worker
@@ -218,7 +218,8 @@ def test_gene_range_equals_the_rows_of_the_whole_call(kernel, case, storage, sin
 # ---------------------------------------------------------------------------------------------------------- the 32-bit row index
 @pytest.fixture(scope="module")
 def big():
-    """One allocation for the five tests: 2^31 + 2 gene_stride + Nc uint16 elements, every byte 0xFF; freed when the module is done."""
+    """One allocation for the row-index tests of a module (this one's five; tests/test_hip_cabi_layouts_six.py takes the fixture over
+    for its six): 2^31 + 2 gene_stride + Nc + BIG_U_OFFSET uint16 elements, every byte 0xFF; freed when the module is done."""
     free, _ = torch.cuda.mem_get_info()
     if free < L.BIG_FREE_NEEDED:
         pytest.skip(f"the 32-bit row-index tests need {L.BIG_FREE_NEEDED} bytes free on the device ({2 * L.BIG_TOTAL} in one allocation); "
